@@ -21,9 +21,17 @@ collective inside the timed work; value = max-over-ranks time ÷ all songs.
 
 Prints ONE JSON line on rank 0.  ``roofline`` is the dominant kernel (the
 SwiGLU gate/up GEMM, 2·M·N·K algorithmic FLOPs per launch) timed with HIP
-events around every launch inside the timed region; ``cpu_baseline`` is the
-CPU oracle (PyTorch fp32) timed on this host for one full-size CFG DiT step +
-a 64-frame VAE window, extrapolated to the song.
+events around every launch inside the timed region.
+
+A plain run sets up, warms up, times the ``--steps`` songs and prints the line.
+``--dump-outputs DIR`` also writes what the last timed step returned
+(``target_latents``, a seeded sample of ``wav``) as ``DIR/<name>.npy``; weights,
+conditioning and seeds are fixed, so the same arguments give the same inputs.
+``--full`` adds, after the timed steps: ``kernels`` (one extra song with every
+kernel family timed), ``output_leg`` (the post-decode leg against the
+reference's host leg) and ``cpu_baseline`` / ``cpu_baseline_config1`` (the CPU
+oracle, PyTorch fp32, timed on this host for one full-size CFG DiT step + a
+64-frame VAE window and extrapolated to the song; config 1 run in full).
 """
 from __future__ import annotations
 
@@ -80,7 +88,33 @@ def parse():
                    help="skip the post-decode output leg measurement (D->H, PCM16 conversion, WAV write)")
     p.add_argument("--no-config1", action="store_true",
                    help="skip the CPU run of BASELINE config 1 (10 s turbo, 8 steps, fp32, in full)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what the headline figure does not need: the "
+                        "per-kernel breakdown (one extra song), the output leg, the CPU baselines "
+                        "(--no-output-leg / --no-cpu-baseline / --no-config1 drop single parts)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32: "
+                        "target_latents in full, wav as a fixed seeded sample of its elements")
     return p.parse_args()
+
+
+DUMP_WAV_SAMPLES = 1 << 22    # elements of the decoded audio kept by --dump-outputs (16 MiB as float32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as path/<name>.npy in float32.  A tensor above DUMP_WAV_SAMPLES
+    elements is written as a sample of its flattened elements at indices drawn from a fixed seed
+    (the same indices for the same shape), so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().float().cpu().contiguous().numpy()
+        if a.size > DUMP_WAV_SAMPLES:
+            idx = np.sort(np.random.default_rng(20240).integers(0, a.size, size=DUMP_WAV_SAMPLES))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def host_cpus():
@@ -279,10 +313,13 @@ def dry_run(args, rank, world):
         song(10_000 + rank * 100 + i)
     D.barrier()
     t0 = time.time()
+    last = None
     for i in range(args.steps):
-        song(rank * 1000 + i)
+        last = song(rank * 1000 + i)
     D.barrier()
     elapsed_max = D.max_over_ranks(time.time() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"song": last})
     bc_all = D.gather_floats([bcast_ms])
     songs = args.steps * world
     if rank == 0:
@@ -432,6 +469,8 @@ def main():
                   lyric_hidden_states=te.embed_tokens(lyric_ids.expand(Bw, -1).contiguous()), seed=seeds)
         return kw
 
+    last_result = [None]     # rank 0, --dump-outputs: what the latest pipe.generate returned
+
     def song(idx, warm=False):
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -448,7 +487,9 @@ def main():
         sampler = dict(infer_steps=args.infer_steps, diffusion_guidance_sale=args.guidance, shift=args.shift,
                        infer_method="ode")
         if rank == 0:
-            pipe.generate(**batch_kwargs(seeds), **sampler)
+            res = pipe.generate(**batch_kwargs(seeds), **sampler)
+            if args.dump_outputs:
+                last_result[0] = res
         else:
             pipe.serve_one()
         e1, e2 = pipe.last_events
@@ -468,11 +509,17 @@ def main():
     elapsed = time.time() - t0
     elapsed_max = D.max_over_ranks(elapsed, dev)
     prof = rt.profile_read()
-    # per-kernel breakdown from one extra, untimed song with every family timed
-    rt.profile(True)
-    song(999)
-    torch.cuda.synchronize()
-    prof_all = rt.profile_read()
+    if args.dump_outputs and rank == 0 and last_result[0] is not None:
+        # before any further song overwrites the buffers the last timed step returned
+        res = last_result[0]
+        dump_outputs(args.dump_outputs, {"target_latents": res["target_latents"], "wav": res["wav"]})
+    prof_all = None
+    if args.full:
+        # per-kernel breakdown from one extra, untimed song with every family timed
+        rt.profile(True)
+        song(999)
+        torch.cuda.synchronize()
+        prof_all = rt.profile_read()
     rt.profile(False)
     dit_ms = sum(a.elapsed_time(b) for a, b, _ in evs) / args.steps
     vae_ms = sum(b.elapsed_time(c) for _, b, c in evs) / args.steps
@@ -527,7 +574,6 @@ def main():
                         "traffic = FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE per call"}
     except Exception:
         pass
-    kernels = {k: {"launches": n, "avg_us": (ms / n * 1e3 if n else None)} for k, (n, ms) in prof_all.items()}
 
     out = {
         "metric": f"seconds/song ({args.seconds:g} s audio, {args.infer_steps} DiT steps)",
@@ -566,14 +612,18 @@ def main():
         "broadcast_ms_per_rank": [round(v, 3) for v in bcast_all],
         "vae_tflops": round(vae_flops_song / (vae_ms * 1e-3) / 1e12, 1) if vae is not None else None,
         "roofline": roofline,
-        "kernels": kernels,
-        "kernels_note": "per-launch averages (HIP events on the forward stream) from one extra untimed song; the timed region carries events only around the roofline kernel",
+        "full": args.full,
     }
-    if rank == 0 and world == 1 and vae is not None and not args.no_output_leg:
+    if prof_all is not None:
+        out["kernels"] = {k: {"launches": n, "avg_us": (ms / n * 1e3 if n else None)}
+                          for k, (n, ms) in prof_all.items()}
+        out["kernels_note"] = ("per-launch averages (HIP events on the forward stream) from one extra untimed "
+                               "song; the timed region carries events only around the roofline kernel")
+    if args.full and rank == 0 and world == 1 and vae is not None and not args.no_output_leg:
         leg = output_leg(pipe, song, dev, sec_per_song)
         out["output_ms_per_song"] = leg["acehip_serial_leg_ms"]["total_ms"]
         out["output_leg"] = leg
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # a short song (10 s, 8 turbo steps) runs in full; longer ones
         # time one DiT step + one 64-frame VAE window and extrapolate
         full = T <= 250

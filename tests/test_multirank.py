@@ -66,6 +66,23 @@ def test_bench_gpus2_spawns_two_ranks():
     assert len(j["broadcast_ms_per_rank"]) == 2
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs writes the last timed step's result as float32 .npy, identical from run to
+    run for the same arguments; --steps sets the timed steps and --full is accepted."""
+    import numpy as np
+    arrs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        p = _bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run", "--dump-outputs", str(d), *extra])
+        assert p.returncode == 0, p.stderr[-2000:]
+        j = _last_json(p.stdout)
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["song.npy"]
+        arrs.append(np.load(d / "song.npy"))
+    assert arrs[0].dtype == np.float32 and arrs[0].shape == (128, 128) and np.isfinite(arrs[0]).all()
+    assert np.array_equal(arrs[0], arrs[1])
+
+
 def test_bench_under_torchrun():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(29600 + os.getpid() % 300),

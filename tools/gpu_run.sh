@@ -7,7 +7,7 @@
 # stops at the first failure (no GPU step runs after a fault, abort or time-out).  Steps:
 #   tests[=pytest -k expr]     pytest -m gpu (one process, per-test 120 s thread timeout)
 #   smoke                      __graft_entry__.smoke()
-#   bench[=bench.py args]      bench.py (default: --steps 2 --warmup 1), JSON line to <TAG>_bench.json
+#   bench[=bench.py args]      bench.py (default: --full --steps 2 --warmup 1), JSON line to <TAG>_bench.json
 #   stats[=bench.py args]      rocprofv3 --kernel-trace --stats of a bench run → gpurun_out/<TAG>_stats/
 #   pmc=COUNTERS[=bench args]  one rocprofv3 --pmc pass (counters space-separated) → gpurun_out/<TAG>_pmc_N/
 #   py=SCRIPT[=args]           python -u SCRIPT args (A/B tools, micro-benchmarks)
@@ -47,7 +47,7 @@ for step in "$@"; do
         smoke)
             run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
         bench)
-            run bench 600 python -u bench.py ${arg:---steps 2 --warmup 1}
+            run bench 600 python -u bench.py ${arg:---full --steps 2 --warmup 1}
             grep '^{' gpurun_out/${TAG}_bench.log | tail -1 > gpurun_out/${TAG}_bench.json ;;
         stats)
             run stats 600 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_stats -o run -- \
