@@ -34,6 +34,7 @@ EXPORTS = [
     "acehip_rmsnorm_bf16", "acehip_gemm_headpost_bf16", "acehip_attention_masked_bf16",
     "acehip_enc_create", "acehip_enc_set_weight", "acehip_enc_finalize", "acehip_enc_embed",
     "acehip_enc_forward", "acehip_enc_destroy", "acehip_fsq_quantize", "acehip_fsq_codes_from_indices",
+    "acehip_attention_probs_bf16", "acehip_dit_forward_capture",
 ]
 
 
@@ -59,6 +60,12 @@ class VAECfg(ctypes.Structure):
                 ("with_encoder", c_int)]
 
 
+class AttnCapture(ctypes.Structure):
+    """acehip_attn_capture (include/acehip.h)."""
+    _fields_ = [("n", c_int), ("layer", POINTER(c_int)), ("head", POINTER(c_int)), ("k0", c_int), ("k1", c_int),
+                ("out", POINTER(c_float)), ("stop_after_last", c_int)]
+
+
 _LIB = None
 
 
@@ -75,6 +82,8 @@ def _declare(lib):
         "acehip_dit_set_condition": (c_int, [P, P, c_int, c_int, P]),
         "acehip_dit_set_uniform_rows": (c_int, [P, c_int, P]),
         "acehip_dit_forward": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, P]),
+        "acehip_dit_forward_capture": (c_int, [P, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P,
+                                               POINTER(AttnCapture), P]),
         "acehip_dit_destroy": (c_int, [P]),
         "acehip_dit_set_graph": (c_int, [P, c_int]),
         "acehip_dit_set_timesteps": (c_int, [P, P, P, c_int, P]),
@@ -105,6 +114,8 @@ def _declare(lib):
                                           c_float, P]),
         "acehip_attention_masked_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                                  c_float, P, P]),
+        "acehip_attention_probs_bf16": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int,
+                                                c_int, c_int, c_float, P, P]),
         "acehip_enc_create": (c_int, [c_int, POINTER(EncCfg), POINTER(c_void_p)]),
         "acehip_enc_set_weight": (c_int, [P, c_char_p, P, c_int, c_int, POINTER(c_int64), c_int]),
         "acehip_enc_finalize": (c_int, [P]),

@@ -138,6 +138,45 @@ class DiTRuntime:
                                        ptr(out), stream_ptr()), "dit_forward")
         return out
 
+    def forward_capture(self, xt: torch.Tensor, ctx: torch.Tensor, t: torch.Tensor, pairs, k0: int, k1: int,
+                        t_r: Optional[torch.Tensor] = None, stop_early: bool = True,
+                        out: Optional[torch.Tensor] = None):
+        """forward() plus the cross-attention maps of the (layer, head) ``pairs``
+        (acehip_dit_forward_capture).  Returns ``(maps, vt)``: maps fp32 [n, Bc, k1-k0, S]
+        (S = ceil(T / 2)) in the order of ``pairs``, softmax over all Lenc encoder positions,
+        keys [k0, k1) kept; vt is None with ``stop_early`` (the forward returns after the
+        highest selected layer's cross-attention), else bit-identical to forward()."""
+        Bx, T, _ = xt.shape
+        Bc = self.Bc
+        assert Bc is not None, "set_condition first"
+        assert xt.dtype == self.dtype and ctx.dtype == self.dtype, (xt.dtype, ctx.dtype, self.dtype)
+        assert xt.is_contiguous() and ctx.is_contiguous() and ctx.shape[:2] == xt.shape[:2]
+        pairs = [(int(l), int(h)) for l, h in pairs]
+        n = len(pairs)
+        if not 1 <= n <= 64:
+            raise ValueError(f"forward_capture: 1..64 (layer, head) pairs, got {n}")
+        k0, k1 = int(k0), int(k1)
+        if not 0 <= k0 < k1 <= self.Lenc:
+            raise ValueError(f"forward_capture: key range [{k0}, {k1}) outside [0, {self.Lenc}]")
+        if t_r is None:
+            t_r = t
+        stride = 0 if t.numel() == 1 else 1
+        S = (T + 1) // 2
+        maps = torch.empty(n, Bc, k1 - k0, S, device=xt.device, dtype=torch.float32)
+        vt = None
+        if not stop_early:
+            vt = out if out is not None else torch.empty(Bc, T, 64, device=xt.device, dtype=self.dtype)
+            assert vt.dtype == self.dtype and vt.is_contiguous()
+        layers = (_ffi.c_int * n)(*[p[0] for p in pairs])
+        heads = (_ffi.c_int * n)(*[p[1] for p in pairs])
+        cap = _ffi.AttnCapture(n=n, layer=layers, head=heads, k0=k0, k1=k1,
+                               out=_ffi.ctypes.cast(maps.data_ptr(), _ffi.POINTER(_ffi.c_float)),
+                               stop_after_last=1 if stop_early else 0)
+        dt = ACEHIP_F32 if self.dtype == torch.float32 else ACEHIP_BF16
+        check(lib().acehip_dit_forward_capture(self.h, ptr(xt), ptr(ctx), Bx, ptr(t), ptr(t_r), stride, Bc, T, dt,
+                                               ptr(vt), _ffi.ctypes.byref(cap), stream_ptr()), "dit_forward_capture")
+        return maps, vt
+
     def set_timesteps(self, t: torch.Tensor, t_r: Optional[torch.Tensor] = None):
         """Timestep MLPs of a whole schedule (one broadcast t per step, fp32 device tensor of
         n steps); forward_step(i) then runs step i without re-reading the MLP weights."""
@@ -279,6 +318,14 @@ def takes_timesteps(model) -> bool:
         return False
 
 
+def config_pairs(layers_config: Dict[int, List[int]]) -> List[tuple]:
+    """``{layer: [heads]}`` → [(layer, head)] in dict order, then list order."""
+    pairs = [(int(l), int(h)) for l, hs in layers_config.items() for h in hs]
+    if not pairs:
+        raise ValueError("layers_config selects no (layer, head) pair")
+    return pairs
+
+
 class AceStepDiTBackend:
     """Drop-in for ``AceStepConditionGenerationModel.generate_audio``."""
 
@@ -411,6 +458,32 @@ class AceStepDiTBackend:
                 self.rt.set_uniform_rows(B)
             return
         self.rt.set_condition(enc)
+
+    def cross_attention_maps(self, xt: torch.Tensor, t: torch.Tensor, enc: torch.Tensor, ctx: torch.Tensor,
+                             layers_config: Dict[int, List[int]], k0: int, k1: int,
+                             stop_early: bool = True) -> torch.Tensor:
+        """Cross-attention maps of ``layers_config`` ({layer: [heads]}) for one decoder forward at
+        ``t_r = t`` — what ``decoder(..., output_attentions=True, custom_layers_config,
+        enable_early_exit=True)`` (base:1303-1507) is called for by the lyric aligners.
+
+        xt [B, T, 64], ctx [B, T, 128], enc [B, Lenc, D] (pre condition_embedder), t: B
+        timesteps (or one, broadcast).  Returns fp32 [n, B, k1-k0, S] on the device, already
+        [tokens, frames]; n runs over ``layers_config`` in dict order, then list order (the
+        order ``MusicStampsAligner._preprocess_attention`` stacks in, dit_alignment.py:129-140).
+
+        It calls ``set_condition(enc)`` itself (uniform rows off), so it OVERWRITES the
+        handle's cross K/V cache; ``generate_audio`` re-sets the cache on every request, so
+        that is harmless."""
+        pairs = config_pairs(layers_config)
+        dtype, device = self.dtype, self.device
+        self.rt.set_condition(enc.to(device=device, dtype=dtype))     # resets uniform rows
+        xt = xt.to(device=device, dtype=dtype).contiguous()
+        ctx = ctx.to(device=device, dtype=dtype).contiguous()
+        # timesteps reach the kernels as fp32 holding model-dtype values (acehip_dit_forward)
+        t = torch.as_tensor(t, device=device).to(dtype).float().reshape(-1).contiguous()
+        assert t.numel() in (1, enc.shape[0]), (t.numel(), enc.shape[0])
+        maps, _ = self.rt.forward_capture(xt, ctx, t, pairs, k0, k1, stop_early=stop_early)
+        return maps
 
     def _base_loop(self, kw, enc, ctx, enc_nc, ctx_nc, acs):
         dtype, device = self.dtype, self.device

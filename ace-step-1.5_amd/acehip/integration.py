@@ -31,6 +31,16 @@ Seams:
              ``lora/controls.py:12-157``) change the decoder's effective weights;
              :func:`install` wraps them so the merged weights are re-packed into the
              handle afterwards (:func:`refresh_decoder_weights`).
+  * lyrics — ``handler.get_lyric_timestamp`` / ``handler.get_lyric_score``
+             (``handler/lyric_timestamp.py:15-147``, ``lyric_score.py:15-166``; the LRC
+             button and the score of ``ui/gradio/events/results``) call
+             ``self.model.decoder(..., output_attentions=True, custom_layers_config,
+             enable_early_exit=True)``: replaced by :class:`~acehip.alignment.LyricAlignment`,
+             which takes the selected heads' cross-attention maps from the DiT handle
+             (``acehip_dit_forward_capture``: the re-packed weights, LoRA included, a stop
+             after the highest selected layer) and hands them to the reference's own aligners.
+             The capture overwrites the handle's cross K/V cache; ``generate_audio`` re-sets
+             it on every request.
 
 Failure policy: by default an acehip error propagates (the request fails
 loudly, ``generate_music.py:181-190`` turns it into an error payload).  The
@@ -47,6 +57,7 @@ import torch
 
 from .condition import AudioDetokenizer, AudioTokenizer, ConditionEncoder, HipPrepareCondition, TextEncoder
 from .config import VAEConfig
+from .alignment import LyricAlignment
 from .dit import AceStepDiTBackend
 from .vae import OobleckBackend
 
@@ -118,8 +129,10 @@ _LORA_METHODS = ("add_lora", "load_lora", "add_voice_lora", "remove_lora", "unlo
 
 
 def install(handler, max_seconds: float = 600.0, max_batch: int = 8, fallback: bool = False,
-            vae: bool = True, condition: bool = True, text_encoder: bool = True) -> dict:
-    """Swap the handler's DiT sampler, VAE and (Qwen3) text encoder for the acehip backends."""
+            vae: bool = True, condition: bool = True, text_encoder: bool = True,
+            lyric_alignment: bool = True) -> dict:
+    """Swap the handler's DiT sampler, VAE, (Qwen3) text encoder and the decoder call of its
+    lyric timestamp / score methods for the acehip backends."""
     dit = AceStepDiTBackend.from_reference_model(handler.model, max_seconds=max_seconds,
                                                  max_batch=max_batch)
     if condition:
@@ -155,6 +168,9 @@ def install(handler, max_seconds: float = 600.0, max_batch: int = 8, fallback: b
     out = {"dit": dit}
     if condition:
         out["prepare_condition"] = out_prep
+
+    if lyric_alignment and (hasattr(handler, "get_lyric_timestamp") or hasattr(handler, "get_lyric_score")):
+        out["lyric_alignment"] = LyricAlignment(handler, dit, fallback=fallback).bind()
 
     # LoRA lifecycle: after any adapter change re-pack the merged decoder weights
     for meth in _LORA_METHODS:

@@ -293,5 +293,13 @@ def synth_null_condition(cfg: DiTConfig, seed: int = 0, **kw) -> torch.Tensor:
         "null_condition_emb"]
 
 
+def synth_encoder_states(cfg: DiTConfig, batch: int, length: int, seed: int = 0, gain: float = 1.0) -> torch.Tensor:
+    """Encoder hidden states [batch, length, D] = gain · N(0, 1), fp32, from the same NumPy
+    PCG64 streams as the weights: fixtures whose encoder input would not fit a committed file
+    regenerate it from (seed, gain) and pin it with a checksum."""
+    w = synth_weights({"encoder_states.null_condition_emb": (batch, length, cfg.hidden_size)}, seed, "bench")
+    return w["encoder_states.null_condition_emb"] * float(gain)
+
+
 def synth_vae_weights(cfg: VAEConfig, seed: int = 0, mode: str = "bench", with_encoder=True, **kw):
     return synth_weights(vae_weight_shapes(cfg, with_encoder), seed, mode, **kw)

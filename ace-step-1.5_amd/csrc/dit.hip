@@ -120,17 +120,20 @@ struct acehip_dit {
     } f{};
 };
 
-static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, hipStream_t s);
+static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, hipStream_t s,
+                        const acehip_attn_capture *cap = nullptr);
 static int timestep_mlps(acehip_dit *h, const bf16_t *const emb[2], int rows, bf16_t *h1, bf16_t *const temb_e[2],
                          bf16_t *const proj_e[2], bf16_t *temb, bf16_t *proj, hipStream_t s);
 static int forward_bf16(acehip_dit *h, const void *xt, const void *ctx, int Bx, const float *t, const float *t_r,
-                        int t_stride, int step, int Bc, int T, void *vt_out, hipStream_t s);
+                        int t_stride, int step, int Bc, int T, void *vt_out, hipStream_t s,
+                        const acehip_attn_capture *cap = nullptr);
 static int create_f32(acehip_dit *h);
 static int set_weight_f32(acehip_dit *h, Slot &s, const void *ptr, int dtype, int64_t n, int on_device);
 static int build_rope_f32(acehip_dit *h);
 static int set_condition_f32(acehip_dit *h, const float *enc, int Bc, int Lenc, hipStream_t s);
 static int forward_f32(acehip_dit *h, const float *xt, const float *ctx, int Bx, const float *t, const float *t_r,
-                       int t_stride, int Bc, int T, float *vt_out, hipStream_t s);
+                       int t_stride, int Bc, int T, float *vt_out, hipStream_t s,
+                       const acehip_attn_capture *cap = nullptr);
 
 // every GEMM of this runtime may use the handle's split-K workspace (small-M grids)
 static inline int hgemm(acehip_dit *h, GemmArgs g, hipStream_t s, RowAdd *defer = nullptr) {
@@ -609,6 +612,45 @@ int acehip_dit_forward(acehip_dit *h, const void *xt, const void *ctx, int Bx, c
     return forward_bf16(h, xt, ctx, Bx, t, t_r, t_stride, -1, Bc, T, vt_out, s);
 }
 
+int acehip_dit_forward_capture(acehip_dit *h, const void *xt, const void *ctx, int Bx, const float *t,
+                               const float *t_r, int t_stride, int Bc, int T, int dtype, void *vt_out,
+                               const acehip_attn_capture *cap, void *stream) {
+    if (!h || !xt || !ctx || !t || !t_r || !cap) return fail(ACEHIP_E_ARG, "forward_capture: null argument");
+    if (!h->finalized || !h->have_cond)
+        return fail(ACEHIP_E_STATE, "forward_capture before finalize/set_condition");
+    if (Bc != h->cond_Bc) return fail(ACEHIP_E_ARG, "forward_capture: Bc differs from set_condition");
+    if (dtype != (h->f32 ? ACEHIP_F32 : ACEHIP_BF16))
+        return fail(ACEHIP_E_ARG, "forward_capture: dtype must be the handle's (ACEHIP_F32 with cfg.fp32, else ACEHIP_BF16)");
+    const int S = (T + 1) / 2;
+    if (T <= 0 || S > h->cfg.max_S || Bx <= 0 || Bc % Bx)
+        return fail(ACEHIP_E_ARG, "forward_capture: T/Bx out of range");
+    if (cap->n < 1 || cap->n > 64) return fail(ACEHIP_E_ARG, "forward_capture: cap->n must be in [1, 64]");
+    if (!cap->layer || !cap->head || !cap->out)
+        return fail(ACEHIP_E_ARG, "forward_capture: cap->layer / head / out must be set");
+    if (!vt_out && !cap->stop_after_last)
+        return fail(ACEHIP_E_ARG, "forward_capture: vt_out may be NULL only with stop_after_last");
+    for (int i = 0; i < cap->n; ++i) {
+        if (cap->layer[i] < 0 || cap->layer[i] >= h->L)
+            return fail(ACEHIP_E_ARG, "forward_capture: layer " + std::to_string(cap->layer[i]) + " outside [0, " +
+                                          std::to_string(h->L) + ")");
+        if (cap->head[i] < 0 || cap->head[i] >= h->cfg.heads)
+            return fail(ACEHIP_E_ARG, "forward_capture: head " + std::to_string(cap->head[i]) + " outside [0, " +
+                                          std::to_string(h->cfg.heads) + ")");
+    }
+    if (cap->k0 < 0 || cap->k0 >= cap->k1 || cap->k1 > h->cond_Lenc)
+        return fail(ACEHIP_E_ARG, "forward_capture: key range must satisfy 0 <= k0 < k1 <= Lenc (" +
+                                      std::to_string(h->cond_Lenc) + ")");
+    if (h->uniform_from < Bc)
+        return fail(ACEHIP_E_STATE, "forward_capture: uniform rows are set (acehip_dit_set_uniform_rows); their "
+                                    "cross-attention maps are not computed");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->f32)
+        return forward_f32(h, (const float *)xt, (const float *)ctx, Bx, t, t_r, t_stride, Bc, T, (float *)vt_out, s,
+                           cap);
+    return forward_bf16(h, xt, ctx, Bx, t, t_r, t_stride, -1, Bc, T, vt_out, s, cap);
+}
+
 int acehip_dit_set_graph(acehip_dit *h, int enable) {
     if (!h) return fail(ACEHIP_E_ARG, "null handle");
     h->graph_on = enable != 0 && !h->f32;
@@ -662,7 +704,8 @@ int acehip_dit_forward_step(acehip_dit *h, const void *xt, const void *ctx, int 
 // buffers (emb, Xin, weights, K/V cache), so it can be captured once and replayed.
 // bf16 forward; step >= 0 takes the timestep MLP outputs from the set_timesteps cache
 static int forward_bf16(acehip_dit *h, const void *xt, const void *ctx, int Bx, const float *t, const float *t_r,
-                        int t_stride, int step, int Bc, int T, void *vt_out, hipStream_t s) {
+                        int t_stride, int step, int Bc, int T, void *vt_out, hipStream_t s,
+                        const acehip_attn_capture *cap) {
     const int S = (T + 1) / 2;
     const int M = Bc * S;
     int rc;
@@ -681,7 +724,10 @@ static int forward_bf16(acehip_dit *h, const void *xt, const void *ctx, int Bx, 
     // identical until the first cross-attention — proj_in and layer 0's self-attention
     // block run on row 0 only and are copied (ACEHIP_DIT_DEDUP=0 disables, for A/B)
     const bool dup = Bx == 1 && Bc > 1 && (ts_cached || t_stride == 0) && knobs().dit_dedup;
-    if (!h->graph_on || h->prof) {
+    if (cap) {   // map capture: always eager; stop_after_last ends inside the layer loop
+        RUN(forward_body(h, Bc, S, dup, ts_cached, s, cap));
+        if (cap->stop_after_last) return 0;
+    } else if (!h->graph_on || h->prof) {
         RUN(forward_body(h, Bc, S, dup, ts_cached, s));
     } else {
         const int key[6] = {Bc, S, h->cond_Lenc, std::min(h->uniform_from, Bc), (dup ? 1 : 0) | (ts_cached ? 2 : 0),
@@ -739,7 +785,29 @@ static int timestep_mlps(acehip_dit *h, const bf16_t *const emb[2], int rows, bf
     return 0;
 }
 
-static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, hipStream_t s) {
+// the capture's entries of layer l (heads + their output slots); returns how many
+static int capture_layer(const acehip_attn_capture *cap, int l, AttnProbsSel &sel) {
+    sel.n = 0;
+    for (int i = 0; i < cap->n; ++i)
+        if (cap->layer[i] == l) {
+            sel.head[sel.n] = (int16_t)cap->head[i];
+            sel.slot[sel.n] = (int16_t)i;
+            ++sel.n;
+        }
+    return sel.n;
+}
+static int capture_last_layer(const acehip_attn_capture *cap) {
+    int last = 0;
+    for (int i = 0; i < cap->n; ++i) last = std::max(last, cap->layer[i]);
+    return last;
+}
+
+// cap != null (acehip_dit_forward_capture): the selected heads' softmax rows of each captured
+// layer are written from the cross-Q and the cross K cache; with stop_after_last the body
+// returns right after the last captured layer's maps (X is not read again, so a pending
+// deferred epilogue is dropped and norm_out is not run)
+static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, hipStream_t s,
+                        const acehip_attn_capture *cap) {
     const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, L = h->L, M = Bc * S;
     const int H = h->cfg.heads, KV = h->cfg.kv_heads, Le = h->cond_Lenc;
     const float eps = h->cfg.eps, scale = 1.0f / sqrtf((float)h->cfg.head_dim);
@@ -803,6 +871,12 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
             cq.hp.B = Bq; cq.hp.S = S; cq.hp.nq = H; cq.hp.qw = ly.cqn; cq.hp.q = h->Qh; cq.hp.S_dst = S;
             cq.hp.eps = eps;
             RUN(hgemm(h, cq, s));
+            AttnProbsSel sel;
+            if (cap && capture_layer(cap, l, sel)) {
+                RUN(attention_probs(h->Qh, h->Kc + l * cper, Bq, H, KV, S, Le, sel, cap->k0, cap->k1, scale, cap->out,
+                                    s));
+                if (cap->stop_after_last && l == capture_last_layer(cap)) return 0;
+            }
             RUN(timed(h, 6, s, [&] {
                 return attention(h->Qh, h->Kc + l * cper, h->Vc + l * cper, h->AO, Bq, H, KV, S, Le, -1, scale, qd,
                                  h->attn_ws, s);
@@ -995,6 +1069,21 @@ int acehip_gemm_headpost_bf16(const void *A, int lda, const void *W, int K, int 
 int acehip_attention_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV,
                           int Sq, int Sk, int window, float scale, void *stream) {
     return acehip_attention_masked_bf16(q, k, v, o, B, H, KV, Sq, Sk, window, scale, nullptr, stream);
+}
+
+int acehip_attention_probs_bf16(const void *q, const void *k, int B, int H, int KV, int Sq, int Sk, const int *heads,
+                                int n, int k0, int k1, float scale, float *out, void *stream) {
+    if (!q || !k || !heads || !out) return fail(ACEHIP_E_ARG, "attention_probs: null argument");
+    if (n < 1 || n > 64) return fail(ACEHIP_E_ARG, "attention_probs: n must be in [1, 64]");
+    AttnProbsSel sel;
+    sel.n = n;
+    for (int i = 0; i < n; ++i) {
+        if (heads[i] < 0 || heads[i] >= H) return fail(ACEHIP_E_ARG, "attention_probs: head index out of range");
+        sel.head[i] = (int16_t)heads[i];
+        sel.slot[i] = (int16_t)i;
+    }
+    return attention_probs((const bf16_t *)q, (const bf16_t *)k, B, H, KV, Sq, Sk, sel, k0, k1, scale, out,
+                           (hipStream_t)stream);
 }
 
 int acehip_attention_masked_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV,
@@ -1206,7 +1295,7 @@ static int set_condition_f32(acehip_dit *h, const float *enc, int Bc, int Lenc, 
 }
 
 static int forward_f32(acehip_dit *h, const float *xt, const float *ctx, int Bx, const float *t, const float *t_r,
-                       int t_stride, int Bc, int T, float *vt_out, hipStream_t s) {
+                       int t_stride, int Bc, int T, float *vt_out, hipStream_t s, const acehip_attn_capture *cap) {
     auto &f = h->f;
     const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, L = h->L, S = (T + 1) / 2, M = Bc * S;
     const int H = h->cfg.heads, KV = h->cfg.kv_heads, Le = h->cond_Lenc;
@@ -1259,6 +1348,11 @@ static int forward_f32(acehip_dit *h, const float *xt, const float *ctx, int Bx,
         cq.src = f.QKV; cq.ld_src = qd; cq.B = Bc; cq.S = S; cq.nq = H; cq.qw = ly.cqn; cq.q = f.Qh;
         cq.S_dst = S; cq.eps = eps;
         RUN(head_post_f32(cq, s));
+        AttnProbsSel sel;
+        if (cap && capture_layer(cap, l, sel)) {   // acehip_dit_forward_capture (see forward_body)
+            RUN(attention_probs_f32(f.Qh, f.Kc + l * cper, Bc, H, KV, S, Le, sel, cap->k0, cap->k1, scale, cap->out, s));
+            if (cap->stop_after_last && l == capture_last_layer(cap)) return 0;
+        }
         AttnF32Args ca{};
         ca.q = f.Qh; ca.k = f.Kc + l * cper; ca.v = f.Vc + l * cper; ca.o = f.AO; ca.o_ld = qd; ca.B = Bc;
         ca.H = H; ca.KV = KV; ca.Sq = S; ca.Sk = Le; ca.window = -1; ca.scale = scale;

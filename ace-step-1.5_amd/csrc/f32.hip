@@ -319,6 +319,65 @@ __global__ void swiglu_f32_kernel(const float *g, const float *u, float *o, int6
     if (i < n) o[i] = silu_exact(g[i]) * u[i];
 }
 
+// Softmax rows of selected heads, fp32 twin of attn_probs.hip (same arguments, unrounded
+// output): out[slot][b][j − k0][s] = softmax_j(scale · q[b, head, s, :] · k[b, kvh, j, :]) for j
+// in [k0, k1), the softmax over all Sk keys.  One thread per query (its q row in registers),
+// 64 queries per block; key tiles of 32 staged in LDS and read as broadcasts.  Pass 1 the
+// running max / sum, pass 2 recomputes the same fmaf chains for the keys of [k0, k1), so a
+// row of out is 64 consecutive frames of one key: a coalesced store.
+__global__ __launch_bounds__(64) void attn_probs_f32_kernel(const float *q, const float *k, int B, int H, int KV,
+                                                            int Sq, int Sk, AttnProbsSel sel, int k0, int k1,
+                                                            float scale, float *out) {
+    __shared__ float Ks[32][128];
+    const int tid = threadIdx.x;
+    const int i = blockIdx.y, b = blockIdx.z;
+    const int head = sel.head[i], kvh = head / (H / KV);
+    const int qi = blockIdx.x * 64 + tid;
+    const float *Q = q + ((int64_t)(b * H + head) * Sq + min(qi, Sq - 1)) * 128;
+    const float *K = k + (int64_t)(b * KV + kvh) * Sk * 128;
+    float qv[128];
+#pragma unroll
+    for (int d = 0; d < 128; d += 4) {
+        const f32x4 v = *(const f32x4 *)(Q + d);
+        qv[d] = v[0]; qv[d + 1] = v[1]; qv[d + 2] = v[2]; qv[d + 3] = v[3];
+    }
+    auto stage = [&](int j0, int jend) {   // keys j0 .. j0+31 (those < jend) into Ks
+        __syncthreads();
+        for (int e = tid; e < 32 * 128; e += 64) {
+            const int j = e >> 7, d = e & 127;
+            Ks[j][d] = j0 + j < jend ? K[(int64_t)(j0 + j) * 128 + d] : 0.f;
+        }
+        __syncthreads();
+    };
+    auto score = [&](int j) {
+        float acc = 0.f;
+#pragma unroll
+        for (int d = 0; d < 128; ++d) acc = fmaf(qv[d], Ks[j][d], acc);
+        return acc * scale;
+    };
+    float m = -INFINITY, l = 0.f;
+    for (int j0 = 0; j0 < Sk; j0 += 32) {
+        stage(j0, Sk);
+        const int nj = min(32, Sk - j0);
+        for (int j = 0; j < nj; ++j) {
+            const float sc = score(j);
+            const float mn = fmaxf(m, sc);
+            l = l * expf(m - mn) + expf(sc - mn);
+            m = mn;
+        }
+    }
+    const int64_t nk = k1 - k0;
+    float *o = out + ((int64_t)sel.slot[i] * B + b) * nk * Sq;
+    for (int j0 = k0; j0 < k1; j0 += 32) {
+        stage(j0, k1);
+        const int nj = min(32, k1 - j0);
+        for (int j = 0; j < nj; ++j) {
+            const float p = expf(score(j) - m) / l;
+            if (qi < Sq) o[(int64_t)(j0 + j - k0) * Sq + qi] = p;
+        }
+    }
+}
+
 inline unsigned blocks(int64_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -352,6 +411,16 @@ int attention_f32(const AttnF32Args &a, hipStream_t s) {
     if (a.H % a.KV) return fail(-1, "attention_f32: heads");
     const int64_t grid = (int64_t)a.B * a.H * ((a.Sq + 63) / 64);
     attention_f32_kernel<<<(unsigned)grid, 256, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int attention_probs_f32(const float *q, const float *k, int B, int H, int KV, int Sq, int Sk, const AttnProbsSel &sel,
+                        int k0, int k1, float scale, float *out, hipStream_t s) {
+    if (!q || !k || !out) return fail(-1, "attention_probs_f32: null argument");
+    if (int rc = attention_probs_check(B, H, KV, Sq, Sk, sel, k0, k1)) return rc;
+    const dim3 grid((unsigned)((Sq + 63) / 64), (unsigned)sel.n, (unsigned)B);
+    attn_probs_f32_kernel<<<grid, 64, 0, s>>>(q, k, B, H, KV, Sq, Sk, sel, k0, k1, scale, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

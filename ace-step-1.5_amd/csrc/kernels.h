@@ -180,6 +180,21 @@ int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int 
               const uint8_t *kmask = nullptr);
 size_t attention_ws_bytes();
 
+// Normalised softmax rows of selected heads (attn_probs.hip; fp32 twin in f32.hip):
+//   out[slot[i]][b][j − k0][s] = softmax_j(scale · q[b, head[i], s, :] · k[b, head[i] / (H/KV), j, :])
+// for j in [k0, k1) ⊂ [0, Sk), the softmax over all Sk keys; q [B][H][Sq][128], k [B][KV][Sk][128],
+// out fp32 [slots][B][k1 − k0][Sq].  bf16: each value rounded to bf16 before the fp32 store.
+struct AttnProbsSel {
+    int n;                 // 1..64
+    int16_t head[64];      // head index of entry i
+    int16_t slot[64];      // its output slot
+};
+int attention_probs_check(int B, int H, int KV, int Sq, int Sk, const AttnProbsSel &sel, int k0, int k1);
+int attention_probs(const bf16_t *q, const bf16_t *k, int B, int H, int KV, int Sq, int Sk, const AttnProbsSel &sel,
+                    int k0, int k1, float scale, float *out, hipStream_t s);
+int attention_probs_f32(const float *q, const float *k, int B, int H, int KV, int Sq, int Sk, const AttnProbsSel &sel,
+                        int k0, int k1, float scale, float *out, hipStream_t s);
+
 // --------------------------------------------------------------- sampler ---
 // element type bf16 (f32 = false) or fp32 (the parity mode)
 int apg_euler(const void *vt, void *xt, void *ra, int B, int T, int C, float guidance, float dt, int apply_cfg,

@@ -148,6 +148,38 @@ int acehip_dit_set_timesteps(acehip_dit *h, const float *t, const float *t_r, in
 int acehip_dit_forward_step(acehip_dit *h, const void *xt, const void *ctx, int Bx, int step, int Bc, int T,
                             int dtype, void *vt_out, void *stream);
 
+/* Cross-attention map capture: which softmax rows acehip_dit_forward_capture writes.
+ * The lyric aligners (handler/lyric_timestamp.py:78-111, lyric_score.py:93-138) use a few
+ * (layer, head) pairs of the decoder's cross-attention and only the lyric tokens of the key
+ * axis; out is already in their [tokens, frames] orientation (the transpose(-1, -2) of
+ * lyric_timestamp.py:100):
+ *   out[i][b][j - k0][s] = softmax_j(scale · q_s · k_j) of layer[i], head[i], batch row b,
+ * the softmax over all Lenc encoder positions (the decoder never masks them,
+ * base:1384-1385).  A bf16 handle rounds each value to bf16 before the fp32 store (the
+ * reference's eager softmax is fp32 then .to(query.dtype)); an fp32 handle stores it
+ * unrounded. */
+typedef struct acehip_attn_capture {
+    int n;                    /* 1..64 selected (layer, head) pairs */
+    const int *layer, *head;  /* host arrays [n], any order; out keeps this order */
+    int k0, k1;               /* encoder positions kept, 0 <= k0 < k1 <= Lenc */
+    float *out;               /* device fp32 [n][Bc][k1-k0][S], S = ceil(T / patch) */
+    int stop_after_last;      /* != 0: return after the cross-attention of the highest selected
+                                 layer; vt_out may be NULL and is not written */
+} acehip_attn_capture;
+
+/* acehip_dit_forward plus the capture; replaces decoder(..., output_attentions=True,
+ * custom_layers_config, enable_early_exit) (base:1303-1507, :352-367).  One extra kernel
+ * launch per captured layer (all of that layer's selected heads), on the cross-Q the
+ * forward computes anyway; no [B, heads, S, Lenc] tensor is formed.  With
+ * stop_after_last == 0, vt_out is bit-identical to acehip_dit_forward on the same
+ * inputs.  Always the eager path (never the HIP-graph replay); nothing is allocated.
+ * ACEHIP_E_STATE if uniform rows are set (acehip_dit_set_uniform_rows: the maps of
+ * skipped rows do not exist); ACEHIP_E_ARG for a layer, head or key range out of
+ * range, n outside 1..64, or vt_out == NULL without stop_after_last. */
+int acehip_dit_forward_capture(acehip_dit *h, const void *xt, const void *ctx, int Bx, const float *t,
+                               const float *t_r, int t_stride, int Bc, int T, int dtype, void *vt_out,
+                               const acehip_attn_capture *cap, void *stream);
+
 /* Replay the pointer-independent middle of acehip_dit_forward (timestep MLPs,
  * modulation, proj_in, the layer stack, norm_out) as one HIP graph, captured
  * once per (Bc, S, Lenc, uniform rows) and re-captured when they change or
@@ -386,6 +418,16 @@ int acehip_attention_bf16(const void *q, const void *k, const void *v, void *o, 
 int acehip_attention_masked_bf16(const void *q, const void *k, const void *v, void *o, int B,
                                  int H, int KV, int Sq, int Sk, int window, float scale,
                                  const uint8_t *kmask, void *stream);
+
+/* Normalised attention probabilities of selected heads, head_dim 128, GQA (single-kernel
+ * entry for tests and profiling; the kernel behind acehip_dit_forward_capture):
+ *   out[i][b][j - k0][s] = softmax_j(scale · q[b, heads[i], s, :] · k[b, heads[i] / (H/KV), j, :])
+ * for j in [k0, k1), the softmax over all Sk keys (no mask), each value rounded to bf16
+ * and stored as fp32.  q bf16 [B,H,Sq,128], k bf16 [B,KV,Sk,128] (16-byte aligned);
+ * heads: host array of n (1..64) head indices; out: device fp32 [n][B][k1-k0][Sq]. */
+int acehip_attention_probs_bf16(const void *q, const void *k, int B, int H, int KV, int Sq, int Sk,
+                                const int *heads /*host, n*/, int n, int k0, int k1, float scale,
+                                float *out /* [n][B][k1-k0][Sq] */, void *stream);
 
 /* Qwen3RMSNorm (+ AdaLN modulation when shift/scale are given) over rows of D
  * (transformers modeling_qwen3.py:59-64; reference base:499,530,1496):
