@@ -35,6 +35,8 @@ EXPORTS = [
     "acehip_enc_create", "acehip_enc_set_weight", "acehip_enc_finalize", "acehip_enc_embed",
     "acehip_enc_forward", "acehip_enc_destroy", "acehip_fsq_quantize", "acehip_fsq_codes_from_indices",
     "acehip_attention_probs_bf16", "acehip_dit_forward_capture",
+    "acehip_enc_kv_create", "acehip_enc_prefill", "acehip_enc_decode",
+    "acehip_attention_decode_ws_bytes", "acehip_attention_decode_bf16", "acehip_lm_head_bf16",
 ]
 
 
@@ -122,6 +124,13 @@ def _declare(lib):
         "acehip_enc_embed": (c_int, [P, P, c_int, P, P]),
         "acehip_enc_forward": (c_int, [P, P, P, c_int, c_int, P, P]),
         "acehip_enc_destroy": (c_int, [P]),
+        "acehip_enc_kv_create": (c_int, [P, c_int, c_int]),
+        "acehip_enc_prefill": (c_int, [P, P, P, c_int, c_int, P, P]),
+        "acehip_enc_decode": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+        "acehip_attention_decode_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
+        "acehip_attention_decode_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_float,
+                                                 P, ctypes.c_size_t, P]),
+        "acehip_lm_head_bf16": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
         "acehip_fsq_quantize": (c_int, [P, c_int, c_int, POINTER(c_int), c_int, P, c_int, P, P]),
         "acehip_fsq_codes_from_indices": (c_int, [P, c_int, POINTER(c_int), c_int, P, c_int, P]),
         "acehip_rmsnorm_bf16": (c_int, [P, P, P, P, c_int64, c_int, P, c_int, c_int, c_float, c_int, P]),

@@ -150,7 +150,7 @@ class TextEncoder:
     ``text_encoder.embed_tokens(ids)``.  The 28 causal Qwen3 decoder layers and the final
     norm run on the ``acehip_enc`` runtime (every layer causal, no embed Linear); the
     embedding lookup is a device gather.  Like the reference call (no ``attention_mask``)
-    the mask is Qwen3Model's default causal one; a padding mask is not supported."""
+    the mask is Qwen3Model's default causal one; an ``attention_mask`` adds key padding to it."""
 
     QWEN3_06B = dict(hidden_size=1024, intermediate_size=3072, num_hidden_layers=28, num_attention_heads=16,
                      num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6, rope_theta=1_000_000.0)
@@ -190,16 +190,21 @@ class TextEncoder:
 
     def __call__(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                  **kwargs) -> TextEncoderOutput:
-        if attention_mask is not None:
-            raise NotImplementedError("TextEncoder: padding masks are not supported (the reference passes none)")
+        # attention_mask [B, S] (1 = attend): causal AND key-padded, Qwen3Model's mask for a padded
+        # batch; None (what the reference passes) is the plain causal mask.  A mask without a zero
+        # is no mask (transformers drops it the same way before SDPA): the unmasked kernels run.
+        # For a mask on the device this test is a device-to-host sync, before the side-stream
+        # hand-off; the tokenizer's masks are host tensors, where it costs nothing
+        if attention_mask is not None and bool((attention_mask != 0).all()):
+            attention_mask = None
         if self._side is None:
             h = self.embed_tokens(input_ids)
-            return TextEncoderOutput(self.stack.forward(h))
+            return TextEncoderOutput(self.stack.forward(h, attention_mask))
         main = torch.cuda.current_stream(self.device)
         self._side.wait_stream(main)                 # input ids (and the weights) ready
         with torch.cuda.stream(self._side):
             h = self.embed_tokens(input_ids)
-            out = self.stack.forward(h)
+            out = self.stack.forward(h, attention_mask)
         ev = torch.cuda.Event()
         ev.record(self._side)
         out.record_stream(main)                      # read on the consumer's stream later

@@ -42,6 +42,14 @@ Seams:
              The capture overwrites the handle's cross K/V cache; ``generate_audio`` re-sets
              it on every request.
 
+  * LM     — ``LLMHandler.llm`` on the ``pt`` backend (the one ROCm users get: nano-vllm needs
+             flash-attn and Triton): the 5 Hz planner's token loops call it only through
+             ``_forward_pass`` (``llm_inference.py:416-438``).  :func:`install_lm` — a separate
+             call on the ``LLMHandler``, :func:`install` does not touch it — replaces it with
+             :class:`~acehip.lm.HipCausalLM` (prefill + one-token decode over a K/V cache in the
+             handle, vocabulary projection); the logits processors, sampling, ``generate()``
+             and scoring (``get_hf_model_for_scoring``) stay in torch.
+
 Failure policy: by default an acehip error propagates (the request fails
 loudly, ``generate_music.py:181-190`` turns it into an error payload).  The
 MLX precedent instead logs and falls back to the PyTorch path
@@ -245,6 +253,39 @@ def install(handler, max_seconds: float = 600.0, max_batch: int = 8, fallback: b
         handler.tiled_encode = tiled_encode
         out["vae"] = vb
     return out
+
+
+def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback: bool = False, runtime=None,
+               **kw) -> dict:
+    """Put the 5 Hz LM's token loop on libacehip: ``llm_handler.llm`` (a transformers
+    ``Qwen3ForCausalLM`` on the ``pt`` backend) becomes a :class:`~acehip.lm.HipCausalLM`.
+
+    Nothing is changed — and the returned dict says why under ``"skipped"`` — when the
+    handler's backend is not ``pt`` or the model's heads / kv_heads ratio is not 1 or 2 (the
+    4B LM).  ``get_hf_model_for_scoring`` is rebound to return the original module
+    (``core/scoring/lm_score.py`` needs logits at every position).  ``fallback=True``: an acehip
+    error in a call is logged and that call and the rest of the generation run on the original
+    module, the policy of :func:`install`.  ``runtime``: an already built
+    :class:`~acehip.lm.HipLMRuntime` (or, in the host tests, a stand-in) instead of one built
+    from the model's weights."""
+    from .lm import HipCausalLM
+    backend = getattr(llm_handler, "llm_backend", None)
+    if backend != "pt":
+        log.info("acehip install_lm: llm_backend is %r, not 'pt'; nothing installed", backend)
+        return {"lm": None, "skipped": f"llm_backend is {backend!r}, not 'pt'"}
+    orig = llm_handler.llm
+    c = orig.config
+    ratio = c.num_attention_heads / c.num_key_value_heads
+    if ratio not in (1, 2):
+        log.info("acehip install_lm: heads / kv_heads = %s (supported: 1, 2); the LM stays on PyTorch", ratio)
+        return {"lm": None, "skipped": f"heads / kv_heads = {ratio:g} (supported: 1 or 2)"}
+    if runtime is not None:
+        lm = HipCausalLM(runtime, wrapped=orig, fallback=fallback)
+    else:
+        lm = HipCausalLM.from_reference_model(orig, max_batch=max_batch, capacity=capacity, fallback=fallback, **kw)
+    llm_handler.llm = lm
+    llm_handler.get_hf_model_for_scoring = lambda: orig
+    return {"lm": lm, "original": orig}
 
 
 def hip_normalize_audio(audio_data: torch.Tensor, target_db: float = -1.0) -> torch.Tensor:

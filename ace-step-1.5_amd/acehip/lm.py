@@ -1,0 +1,286 @@
+"""The 5 Hz language model's token loop on the HIP path.
+
+``LLMHandler.llm`` on the reference's ``pt`` backend is a transformers ``Qwen3ForCausalLM``.
+Its two custom loops (``_generate_with_cfg_custom`` ``acestep/llm_inference.py:2414-2533`` and
+``_generate_with_constrained_decoding`` ``:2321-2412``) touch the model only through
+``_forward_pass`` (``:416-438``):
+
+  * first call:   ``model(input_ids=ids[B, S], attention_mask=mask[B, S], use_cache=True)``
+  * later calls:  ``model(input_ids=ids[:, -1:], past_key_values=past, attention_mask=mask[B, S+i],
+                   use_cache=True)``
+
+and read only ``outputs.logits[:, -1, :]`` and ``outputs.past_key_values``.  :class:`HipCausalLM`
+keeps exactly that contract: the first call embeds and prefills (``acehip_enc_prefill``), every
+later call runs one decode step over the handle's K/V cache (``acehip_enc_decode``), and both
+end in the vocabulary projection (``acehip_lm_head_bf16``).  The batch is ``[cond…, uncond…]``
+left-padded to a common length (``:894-910``); RoPE positions are cache indices, padding
+included, as transformers computes them when no ``position_ids`` are passed.
+
+The FSM-constrained processor, repetition penalty, top-k / top-p, temperature and the
+multinomial stay in torch, where the reference has them.  ``generate()`` (no CFG, no
+constrained decoding, ``:946``) and scoring (``core/scoring/lm_score.py`` needs logits at
+every position) stay on the wrapped module.
+
+The prefill runs on the flash kernels, which take heads / kv_heads of 1 or 2: the 0.6B and
+1.7B LMs (16 / 8).  The 4B LM (32 / 8) stays on PyTorch.
+"""
+from __future__ import annotations
+
+import logging
+from typing import Dict, Iterator, Optional
+
+import torch
+
+from . import _ffi
+from ._ffi import check, lib, ptr, stream_ptr
+from .condition import EncoderStack, _rope_theta
+from .config import DiTConfig
+
+log = logging.getLogger("acehip")
+
+
+class HipLMRuntime:
+    """The native side of :class:`HipCausalLM`: a causal ``acehip_enc`` handle with a K/V cache,
+    the embedding table and the ``lm_head`` weight."""
+
+    def __init__(self, cfg: DiTConfig, device: int = 0, max_batch: int = 16, capacity: int = 8192,
+                 prefill_tokens: Optional[int] = None):
+        self.cfg = cfg
+        self.device = torch.device("cuda", device)
+        self.max_batch, self.capacity = max_batch, capacity
+        # prompt tokens of one prefill (B·S): the activation workspace is sized by it
+        self.prefill_tokens = prefill_tokens or min(max_batch * capacity, 4 * capacity)
+        self.stack = EncoderStack(cfg, cfg.num_hidden_layers, 0, device=device,
+                                  max_tokens=max(self.prefill_tokens, max_batch), max_S=capacity, causal=True)
+        self.table: Optional[torch.Tensor] = None
+        self.w_head: Optional[torch.Tensor] = None
+
+    def load(self, weights: Dict[str, torch.Tensor], lm_head: Optional[torch.Tensor] = None):
+        """Qwen3Model state-dict names; ``lm_head`` [V, hidden] or None (tied to embed_tokens)."""
+        emb = weights["embed_tokens.weight"]
+        self.table = emb.detach().to(self.device, torch.bfloat16).contiguous()
+        tied = lm_head is None or lm_head.data_ptr() == emb.data_ptr()
+        self.w_head = self.table if tied else lm_head.detach().to(self.device, torch.bfloat16).contiguous()
+        self.stack.load({k: v for k, v in weights.items() if k != "embed_tokens.weight"})
+        check(lib().acehip_enc_kv_create(self.stack.h, self.max_batch, self.capacity), "enc_kv_create")
+
+    @property
+    def vocab(self) -> int:
+        return self.w_head.shape[0]
+
+    def embed(self, ids: torch.Tensor) -> torch.Tensor:
+        return torch.nn.functional.embedding(ids.to(self.device), self.table)
+
+    def prefill(self, x: torch.Tensor, kmask: Optional[torch.Tensor]) -> torch.Tensor:
+        """x [B, S, D] bf16, kmask uint8 [B, S] contiguous or None → final-norm rows [B, D]."""
+        x = x.contiguous()
+        B, S, D = x.shape
+        out = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
+        check(lib().acehip_enc_prefill(self.stack.h, ptr(x), ptr(kmask), B, S, ptr(out), stream_ptr()), "enc_prefill")
+        self._keep = (x, kmask)
+        return out
+
+    def decode(self, x: torch.Tensor, kmask: Optional[torch.Tensor], pos: int) -> torch.Tensor:
+        """x [B, D] bf16 at cache index pos; kmask uint8 [rows, ld] over cache positions or None."""
+        x = x.contiguous()
+        B, D = x.shape
+        out = torch.empty(B, D, device=self.device, dtype=torch.bfloat16)
+        ld = kmask.stride(0) if kmask is not None else 0
+        check(lib().acehip_enc_decode(self.stack.h, ptr(x), ptr(kmask), ld, B, pos, ptr(out), stream_ptr()),
+              "enc_decode")
+        self._keep = (x, kmask)
+        return out
+
+    def lm_head(self, h: torch.Tensor) -> torch.Tensor:
+        B, D = h.shape
+        V = self.vocab
+        y = torch.empty(B, V, device=self.device, dtype=torch.bfloat16)
+        check(lib().acehip_lm_head_bf16(ptr(h), D, ptr(self.w_head), ptr(y), V, B, V, D, stream_ptr()), "lm_head")
+        return y
+
+    def close(self):
+        self.stack.close()
+
+
+class HipKVCache:
+    """What ``outputs.past_key_values`` is: a ticket for the K/V cache inside the handle."""
+
+    def __init__(self, owner: "HipCausalLM", generation: int, batch: int, length: int):
+        self._owner, self._generation = owner, generation
+        self.batch, self.length = batch, length
+
+    def get_seq_length(self, layer_idx: int = 0) -> int:
+        return self.length
+
+
+class CausalLMOutput:
+    def __init__(self, logits: torch.Tensor, past_key_values):
+        self.logits = logits
+        self.past_key_values = past_key_values
+
+
+class HipCausalLM:
+    """Drop-in for ``LLMHandler.llm`` on the ``pt`` backend (see the module docstring).
+
+    ``runtime`` provides ``device``, ``max_batch``, ``capacity``, ``embed``, ``prefill``,
+    ``decode`` and ``lm_head`` (:class:`HipLMRuntime`; the host tests inject a stand-in)."""
+
+    def __init__(self, runtime, wrapped=None, fallback: bool = False):
+        self.rt = runtime
+        self.wrapped = wrapped
+        self.fallback = fallback and wrapped is not None
+        self.device = runtime.device
+        self.max_batch, self.capacity = runtime.max_batch, runtime.capacity
+        # key mask over cache positions, and (for the fallback) the tokens fed so far
+        self._mask = torch.zeros(self.max_batch, self.capacity, dtype=torch.uint8, device=self.device)
+        self._ids = (torch.zeros(self.max_batch, self.capacity, dtype=torch.long, device=self.device)
+                     if self.fallback else None)
+        self._masked = False
+        self._generation = 0
+        self._cache: Optional[HipKVCache] = None
+        self._delegating = False     # fallback: the rest of this generation runs on the wrapped module
+
+    @classmethod
+    def from_reference_model(cls, model, max_batch: int = 16, capacity: int = 8192, fallback: bool = False,
+                             device: Optional[int] = None, **kw) -> "HipCausalLM":
+        """From a loaded transformers ``Qwen3ForCausalLM``."""
+        c = model.config
+        cfg = DiTConfig(hidden_size=c.hidden_size, intermediate_size=c.intermediate_size,
+                        num_hidden_layers=c.num_hidden_layers, num_attention_heads=c.num_attention_heads,
+                        num_key_value_heads=c.num_key_value_heads,
+                        head_dim=getattr(c, "head_dim", c.hidden_size // c.num_attention_heads),
+                        rms_norm_eps=c.rms_norm_eps, rope_theta=_rope_theta(c))
+        if device is None:
+            p = next(model.parameters()).device
+            device = p.index or 0 if p.type == "cuda" else 0
+        rt = HipLMRuntime(cfg, device, max_batch=max_batch, capacity=capacity, **kw)
+        # lm_head.weight itself (tied to embed_tokens on the released checkpoints; an untied one works too)
+        sd = model.model.state_dict()
+        head = model.lm_head.weight
+        rt.load(sd, None if head.data_ptr() == sd["embed_tokens.weight"].data_ptr() else head)
+        return cls(rt, wrapped=model, fallback=fallback)
+
+    # ------------------------------------------------------------------ the call contract
+    def __call__(self, input_ids=None, attention_mask=None, past_key_values=None, use_cache=True, **kw):
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("HipCausalLM: input_ids [B, S] is required (inputs_embeds is not supported)")
+        if self._delegating and past_key_values is not None and not isinstance(past_key_values, HipKVCache):
+            return self.wrapped(input_ids=input_ids, attention_mask=attention_mask,
+                                past_key_values=past_key_values, use_cache=use_cache, **kw)
+        if past_key_values is None:
+            self._delegating = False
+            self._check_prefill(input_ids, attention_mask)
+        else:
+            self._check_decode(input_ids, attention_mask, past_key_values)
+        try:
+            if past_key_values is None:
+                return self._prefill(input_ids, attention_mask, use_cache)
+            return self._decode(input_ids, attention_mask, past_key_values)
+        except RuntimeError as e:
+            if not self.fallback:
+                raise
+            log.warning("acehip LM call failed (%s); this generation continues on PyTorch", e)
+            return self._fall_back(input_ids, attention_mask, past_key_values, use_cache, kw)
+
+    forward = __call__
+
+    def _check_prefill(self, ids, mask):
+        B, S = ids.shape
+        if B > self.max_batch or S > self.capacity or S < 1 or B < 1:
+            raise ValueError(f"HipCausalLM: prompt [{B}, {S}] exceeds max_batch {self.max_batch} / "
+                             f"capacity {self.capacity}")
+        limit = getattr(self.rt, "prefill_tokens", None)
+        if limit is not None and B * S > limit:
+            raise ValueError(f"HipCausalLM: prompt [{B}, {S}] has {B * S} tokens, more than the runtime's "
+                             f"prefill_tokens {limit}")
+        if mask is not None and tuple(mask.shape) != (B, S):
+            raise ValueError(f"HipCausalLM: attention_mask {tuple(mask.shape)} does not match input_ids [{B}, {S}]")
+
+    def _check_decode(self, ids, mask, past):
+        if not isinstance(past, HipKVCache) or past._owner is not self:
+            raise ValueError("HipCausalLM: past_key_values is not a cache this model returned (foreign cache)")
+        if past is not self._cache or past._generation != self._generation:
+            raise ValueError("HipCausalLM: past_key_values is stale (a later prefill reset the cache)")
+        B, n = ids.shape
+        if n != 1:
+            raise ValueError(f"HipCausalLM: with past_key_values, input_ids must be [B, 1] (got {n} new tokens)")
+        if B != past.batch:
+            raise ValueError(f"HipCausalLM: batch changed from {past.batch} to {B} within one generation")
+        if past.length >= self.capacity:
+            raise ValueError(f"HipCausalLM: the K/V cache is full (capacity {self.capacity})")
+        if mask is not None and tuple(mask.shape) != (B, past.length + 1):
+            raise ValueError(f"HipCausalLM: attention_mask {tuple(mask.shape)} must be [{B}, {past.length + 1}]")
+
+    def _prefill(self, ids, mask, use_cache):
+        B, S = ids.shape
+        self._generation += 1
+        self._cache = None
+        km = None
+        if mask is not None:
+            km = (mask != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+            self._mask[:B, :S] = km
+        else:
+            self._mask[:B, :S] = 1
+        self._masked = mask is not None
+        if self._ids is not None:
+            self._ids[:B, :S] = ids.to(self.device)
+        h = self.rt.prefill(self.rt.embed(ids), km)
+        logits = self.rt.lm_head(h).unsqueeze(1)
+        if use_cache:
+            self._cache = HipKVCache(self, self._generation, B, S)
+        return CausalLMOutput(logits, self._cache)
+
+    def _decode(self, ids, mask, past):
+        B, pos = past.batch, past.length
+        # column pos of the key mask from the last column of the mask given: a device op
+        if mask is not None:
+            self._mask[:B, pos] = (mask[:, -1] != 0).to(device=self.device, dtype=torch.uint8)
+            self._masked = True
+        else:
+            self._mask[:B, pos] = 1
+        if self._ids is not None:
+            self._ids[:B, pos] = ids[:, 0].to(self.device)
+        h = self.rt.decode(self.rt.embed(ids[:, 0]), self._mask if self._masked else None, pos)
+        logits = self.rt.lm_head(h).unsqueeze(1)
+        past.length = pos + 1
+        return CausalLMOutput(logits, past)
+
+    def _fall_back(self, ids, mask, past, use_cache, kw):
+        """The failing call and the rest of this generation on the wrapped module: it is given
+        the whole sequence so far (prompt and every token fed since) and builds its own cache."""
+        self._delegating = True
+        if past is not None:
+            B, n = past.batch, past.length + 1
+            ids = self._ids[:B, :n].to(ids.device)
+            self._cache = None
+        out = self.wrapped(input_ids=ids, attention_mask=mask, use_cache=use_cache, **kw)
+        return CausalLMOutput(out.logits[:, -1:, :], getattr(out, "past_key_values", None))
+
+    # ------------------------------------------------------------------ pass-throughs
+    @property
+    def config(self):
+        return self.wrapped.config
+
+    @property
+    def generation_config(self):
+        return self.wrapped.generation_config
+
+    def generate(self, *a, **k):
+        """No CFG and no constrained decoding (llm_inference.py:946): transformers' own loop."""
+        return self.wrapped.generate(*a, **k)
+
+    def parameters(self) -> Iterator[torch.Tensor]:
+        """One tensor on the handle's device: ``_load_model_context`` (llm_inference.py:3835-3890)
+        then sees the model as already there."""
+        yield self._mask if getattr(self.rt, "w_head", None) is None else self.rt.w_head
+
+    def to(self, *a, **k) -> "HipCausalLM":
+        return self
+
+    def eval(self) -> "HipCausalLM":
+        return self
+
+    def close(self):
+        close = getattr(self.rt, "close", None)
+        if close:
+            close()

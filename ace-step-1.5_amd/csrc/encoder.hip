@@ -53,6 +53,13 @@ struct acehip_enc {
     bf16_t *X, *XN, *Qh, *Kh, *Vh, *AO, *Hb, *O128;
     void *attn_ws = nullptr;
     void *gemm_ws = nullptr;   // split-K partials for small-M GEMMs
+    // token loop (acehip_enc_kv_create): per-layer K / V caches [L][kv_B][KV][kv_cap][128] and
+    // attn_decode's key-range partials
+    bf16_t *Kc = nullptr, *Vc = nullptr;
+    int kv_B = 0, kv_cap = 0;
+    bool kv_tried = false;     // a kv_create that failed part-way keeps its buffers until destroy: no second attempt
+    void *dec_ws = nullptr;
+    size_t dec_ws_bytes = 0;
 };
 
 // every GEMM of this runtime may use the handle's split-K workspace (small-M grids)
@@ -256,12 +263,12 @@ int acehip_enc_embed(acehip_enc *h, const void *x, int M, void *out, void *strea
     return gemm(g, (hipStream_t)stream);
 }
 
-int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream) {
-    if (!h || !x || !out) return fail(ACEHIP_E_ARG, "null argument");
-    if (!h->finalized) return fail(ACEHIP_E_STATE, "enc_forward before finalize");
-    if (B <= 0 || S <= 0 || S > h->cfg.max_S || (int64_t)B * S > h->cfg.max_tokens)
-        return fail(ACEHIP_E_ARG, "enc_forward: B*S / S out of range");
-    HIP_TRY(hipSetDevice(h->device));
+}  // extern "C"
+
+// acehip_enc_forward's body.  prefill: every layer's K (normed, rotated) and V also land in
+// cache rows [0, S), and out receives only the final-norm row of each sequence's last position.
+static int enc_forward_impl(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream,
+                            bool prefill) {
     hipStream_t s = (hipStream_t)stream;
     const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, M = B * S;
     const int H = h->cfg.heads, KV = h->cfg.kv_heads;
@@ -283,6 +290,13 @@ int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B
         q.hp.cos = h->rope_cos; q.hp.sin = h->rope_sin;
         q.hp.q = h->Qh; q.hp.k = h->Kh; q.hp.v = h->Vh; q.hp.S_dst = S; q.hp.eps = eps;
         RUN(hgemm(h, q, s));
+        if (prefill) {   // [B·KV] blocks of S rows → the same blocks of the cache, kv_cap rows apart
+            const size_t per = (size_t)h->kv_B * KV * h->kv_cap * 128;
+            HIP_TRY(hipMemcpy2DAsync(h->Kc + l * per, (size_t)h->kv_cap * 256, h->Kh, (size_t)S * 256, (size_t)S * 256,
+                                     (size_t)B * KV, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipMemcpy2DAsync(h->Vc + l * per, (size_t)h->kv_cap * 256, h->Vh, (size_t)S * 256, (size_t)S * 256,
+                                     (size_t)B * KV, hipMemcpyDeviceToDevice, s));
+        }
         // layer kind: 0 full, 1 band |i−j| <= window, 2 causal (the Qwen3 text encoder)
         const int win = h->sliding[l] == 2 ? ATTN_CAUSAL : h->sliding[l] ? h->cfg.window : -1;
         RUN(attention(h->Qh, h->Kh, h->Vh, h->AO, B, H, KV, S, S, win, scale, qd, h->attn_ws, s, kmask));
@@ -301,6 +315,12 @@ int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B
         dn.M = M; dn.N = D; dn.K = F; dn.epi = EPI_RES; dn.res = h->X; dn.ldr = D;
         RUN(hgemm(h, dn, s, &pend));
     }
+    if (prefill) {
+        RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, S, h->XN, M, D, eps, s, pend));
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)D * 2, h->XN + (size_t)(S - 1) * D, (size_t)S * D * 2, (size_t)D * 2, B,
+                                 hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
     if (!h->cfg.out_dim) {
         RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, S, (bf16_t *)out, M, D, eps, s, pend));
         return 0;
@@ -312,6 +332,117 @@ int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B
     po.M = M; po.N = 128; po.K = D; po.epi = EPI_STORE; po.bias = h->bout;
     RUN(hgemm(h, po, s));
     RUN(copy_cols(h->O128, 128, (bf16_t *)out, h->cfg.out_dim, M, h->cfg.out_dim, s));
+#undef RUN
+    return 0;
+}
+
+extern "C" {
+
+int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream) {
+    if (!h || !x || !out) return fail(ACEHIP_E_ARG, "null argument");
+    if (!h->finalized) return fail(ACEHIP_E_STATE, "enc_forward before finalize");
+    if (B <= 0 || S <= 0 || S > h->cfg.max_S || (int64_t)B * S > h->cfg.max_tokens)
+        return fail(ACEHIP_E_ARG, "enc_forward: B*S / S out of range");
+    HIP_TRY(hipSetDevice(h->device));
+    return enc_forward_impl(h, x, kmask, B, S, out, stream, false);
+}
+
+// ---- token loop: K/V cache, prefill, one-token decode (acestep/llm_inference.py:416-438) ----
+
+static bool enc_all_causal(const acehip_enc *h) {
+    for (uint8_t k : h->sliding)
+        if (k != 2) return false;
+    return true;
+}
+
+int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity) {
+    if (!h) return fail(ACEHIP_E_ARG, "null handle");
+    if (h->Kc) return fail(ACEHIP_E_STATE, "enc_kv_create: the handle already has a cache");
+    if (h->kv_tried)
+        return fail(ACEHIP_E_STATE, "enc_kv_create: an earlier attempt on this handle failed; destroy the handle "
+                                    "(its partial buffers are freed there) and create a new one");
+    const int G = h->cfg.heads / h->cfg.kv_heads;
+    if (G != 1 && G != 2)
+        return fail(ACEHIP_E_ARG, "enc_kv_create: heads/kv_heads must be 1 or 2 (the prefill's attention kernels); "
+                                  "this model stays on the PyTorch path");
+    if (!enc_all_causal(h) || h->cfg.out_dim)
+        return fail(ACEHIP_E_ARG, "enc_kv_create: needs a causal stack (sliding[l] == 2 for every layer) without proj_out");
+    if (max_B <= 0 || max_B > 65535 || max_B > h->cfg.max_tokens || capacity <= 0 || capacity > h->cfg.max_S)
+        return fail(ACEHIP_E_ARG, "enc_kv_create: need 0 < max_B <= max_tokens and 0 < capacity <= max_S (the RoPE table)");
+    HIP_TRY(hipSetDevice(h->device));
+    h->kv_tried = true;
+    const size_t per = (size_t)max_B * h->cfg.kv_heads * capacity * 128;
+    h->dec_ws_bytes = attention_decode_ws_bytes(max_B, h->cfg.heads);
+    bf16_t *kc = enc_alloc(h, per * h->L), *vc = kc ? enc_alloc(h, per * h->L) : nullptr;
+    void *ws = vc ? enc_alloc(h, h->dec_ws_bytes / 2) : nullptr;
+    if (!ws) return fail(ACEHIP_E_OOM, "enc_kv_create: device allocation failed");   // freed by enc_destroy
+    HIP_TRY(hipMemset(kc, 0, per * h->L * 2));
+    HIP_TRY(hipMemset(vc, 0, per * h->L * 2));
+    h->Kc = kc; h->Vc = vc; h->dec_ws = ws;
+    h->kv_B = max_B; h->kv_cap = capacity;
+    return 0;
+}
+
+int acehip_enc_prefill(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream) {
+    if (!h || !x || !out) return fail(ACEHIP_E_ARG, "null argument");
+    if (!h->finalized) return fail(ACEHIP_E_STATE, "enc_prefill before finalize");
+    if (!h->Kc) return fail(ACEHIP_E_STATE, "enc_prefill: no cache (acehip_enc_kv_create)");
+    if (B <= 0 || B > h->kv_B || S <= 0 || S > h->kv_cap || (int64_t)B * S > h->cfg.max_tokens)
+        return fail(ACEHIP_E_ARG, "enc_prefill: B / S / B*S out of range (cache batch, capacity, max_tokens)");
+    HIP_TRY(hipSetDevice(h->device));
+    return enc_forward_impl(h, x, kmask, B, S, out, stream, true);
+}
+
+int acehip_enc_decode(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int B, int pos, void *out,
+                      void *stream) {
+    if (!h || !x || !out) return fail(ACEHIP_E_ARG, "null argument");
+    if (!h->finalized) return fail(ACEHIP_E_STATE, "enc_decode before finalize");
+    if (!h->Kc) return fail(ACEHIP_E_STATE, "enc_decode: no cache (acehip_enc_kv_create)");
+    if (B <= 0 || B > h->kv_B) return fail(ACEHIP_E_ARG, "enc_decode: B exceeds the cache's batch");
+    if (pos < 0 || pos >= h->kv_cap) return fail(ACEHIP_E_ARG, "enc_decode: pos must be in [0, capacity)");
+    if (kmask && mask_ld < pos + 1) return fail(ACEHIP_E_ARG, "enc_decode: mask_ld < pos + 1");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, cap = h->kv_cap;
+    const int H = h->cfg.heads, KV = h->cfg.kv_heads;
+    const float eps = h->cfg.eps, scale = 1.0f / sqrtf(128.0f);
+    const size_t per = (size_t)h->kv_B * KV * cap * 128;
+    int rc;
+#define RUN(e) do { if ((rc = (e))) return rc; } while (0)
+    HIP_TRY(hipMemcpyAsync(h->X, x, (size_t)B * D * 2, hipMemcpyDeviceToDevice, s));
+    RowAdd pend{};
+    for (int l = 0; l < h->L; ++l) {
+        const auto &ly = h->layers[l];
+        RUN(rmsnorm_mod(h->X, ly.ln1, nullptr, nullptr, 0, 1, h->XN, B, D, eps, s, pend));
+        pend = RowAdd{};
+        // one row per sequence: RoPE row `pos`, q compact [B][H][128], k / v into cache slot pos
+        GemmArgs q{};
+        q.A = h->XN; q.lda = D; q.W = ly.wqkv; q.ldw = D;
+        q.M = B; q.N = qd + 2 * kvd; q.K = D; q.epi = EPI_HEADPOST;
+        q.hp.B = B; q.hp.S = 1; q.hp.nq = H; q.hp.nk = KV; q.hp.nv = KV; q.hp.qw = ly.qn; q.hp.kw = ly.kn;
+        q.hp.cos = h->rope_cos + (size_t)pos * 128; q.hp.sin = h->rope_sin + (size_t)pos * 128;
+        q.hp.q = h->Qh; q.hp.S_dst_q = 1;
+        q.hp.k = h->Kc + l * per + (size_t)pos * 128; q.hp.v = h->Vc + l * per + (size_t)pos * 128;
+        q.hp.S_dst = cap; q.hp.eps = eps;
+        RUN(hgemm(h, q, s));
+        RUN(attention_decode(h->Qh, h->Kc + l * per, h->Vc + l * per, h->AO, B, H, KV, pos + 1, cap, kmask, mask_ld,
+                             scale, h->dec_ws, h->dec_ws_bytes, s));
+        GemmArgs o{};
+        o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
+        o.M = B; o.N = D; o.K = qd; o.epi = EPI_RES; o.res = h->X; o.ldr = D;
+        RUN(hgemm(h, o, s, &pend));
+        RUN(rmsnorm_mod(h->X, ly.ln2, nullptr, nullptr, 0, 1, h->XN, B, D, eps, s, pend));
+        pend = RowAdd{};
+        GemmArgs gu{};
+        gu.A = h->XN; gu.lda = D; gu.W = ly.wgu; gu.ldw = D; gu.C = h->Hb; gu.ldc = F;
+        gu.M = B; gu.N = 2 * F; gu.K = D; gu.epi = EPI_SWIGLU;
+        RUN(hgemm(h, gu, s));
+        GemmArgs dn{};
+        dn.A = h->Hb; dn.lda = F; dn.W = ly.wdown; dn.ldw = F; dn.C = h->X; dn.ldc = D;
+        dn.M = B; dn.N = D; dn.K = F; dn.epi = EPI_RES; dn.res = h->X; dn.ldr = D;
+        RUN(hgemm(h, dn, s, &pend));
+    }
+    RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, 1, (bf16_t *)out, B, D, eps, s, pend));
 #undef RUN
     return 0;
 }

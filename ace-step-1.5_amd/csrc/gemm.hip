@@ -523,8 +523,9 @@ __device__ __forceinline__ void headpost_epilogue(const GemmArgs &a, char *lds, 
     int64_t bstride;
     const int64_t hs = (int64_t)h.S_dst * 128;
     if (head < h.nq) {
-        base = h.q + head * hs;
-        bstride = h.nq * hs;
+        const int64_t hq = h.S_dst_q ? (int64_t)h.S_dst_q * 128 : hs;
+        base = h.q + head * hq;
+        bstride = h.nq * hq;
     } else if (head < nqk) {
         base = h.k + (head - h.nq) * hs;
         bstride = h.nk * hs;
@@ -1279,7 +1280,7 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
     if (a.epi == EPI_HEADPOST) {
         const HeadPostArgs &h = a.hp;
         if (a.N % 256 || h.S <= 0 || (int64_t)h.B * h.S != a.M || (h.nq + h.nk + h.nv) * 128 != a.N ||
-            h.S_dst < h.S || (h.nq && !h.qw) || (h.nk && !h.kw) || (h.cos == nullptr) != (h.sin == nullptr))
+            h.S_dst < h.S || (h.S_dst_q && h.S_dst_q < h.S) || (h.nq && !h.qw) || (h.nk && !h.kw) || (h.cos == nullptr) != (h.sin == nullptr))
             return fail(-1, "gemm: head-post arguments inconsistent with the GEMM shape");
     }
     const Knobs &kn = knobs();

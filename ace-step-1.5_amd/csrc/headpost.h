@@ -81,7 +81,7 @@ __device__ __forceinline__ bf16_t *head_dst(const HeadPostArgs &a, int u, int b,
     nw = nullptr;
     if (u < a.nq) {
         nw = a.qw;
-        return a.q + (((int64_t)b * a.nq + u) * a.S_dst + s) * 128;
+        return a.q + (((int64_t)b * a.nq + u) * (a.S_dst_q ? a.S_dst_q : a.S_dst) + s) * 128;
     }
     if (u < a.nq + a.nk) {
         nw = a.kw;

@@ -58,6 +58,8 @@ struct HeadPostArgs {
     // (fp32 partials summed in split order, then rounded to bf16) instead of src
     const float *part = nullptr; int splits = 0; int64_t plane = 0;
     int m_off = 0;                       // row of the full projection that GEMM row 0 is (tail-split grids)
+    int S_dst_q = 0;                     // rows per head of q where they differ from k / v's S_dst (0: S_dst) —
+                                         // the token loop writes k / v into a cache of `capacity` rows per head
 };
 enum GemmEpi {
     EPI_STORE = 0,       // C = bf16(acc + bias)
@@ -194,6 +196,17 @@ int attention_probs(const bf16_t *q, const bf16_t *k, int B, int H, int KV, int 
                     int k0, int k1, float scale, float *out, hipStream_t s);
 int attention_probs_f32(const float *q, const float *k, int B, int H, int KV, int Sq, int Sk, const AttnProbsSel &sel,
                         int k0, int k1, float scale, float *out, hipStream_t s);
+
+// Single-token attention over a K/V cache (attn_decode.hip): q [B][H][128], k / v
+// [B][KV][cap][128] with n <= cap valid rows, kmask [B][mask_ld] (1 = attend) or null →
+// o [B][H·128].  H/KV in {1, 2, 4}.  ws: attention_decode_ws_bytes(B, H) bytes (fp32 partials of
+// the key ranges, folded in range order) or null (one range per KV head).
+size_t attention_decode_ws_bytes(int B, int H);
+int attention_decode(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int n,
+                     int cap, const uint8_t *kmask, int mask_ld, float scale, void *ws, size_t ws_bytes,
+                     hipStream_t s);
+// y[m][n] = bf16(Σ_k x[m][k]·W[n][k]), M ≤ 16, any N (the LM's vocabulary projection)
+int lm_head(const bf16_t *x, int64_t ldx, const bf16_t *W, bf16_t *y, int64_t ldy, int M, int N, int K, hipStream_t s);
 
 // --------------------------------------------------------------- sampler ---
 // element type bf16 (f32 = false) or fp32 (the parity mode)

@@ -32,6 +32,7 @@
 #ifndef ACEHIP_H
 #define ACEHIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -250,6 +251,32 @@ int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B
                        void *stream);
 int acehip_enc_destroy(acehip_enc *h);
 
+/* Token loop of the 5 Hz language model (a transformers Qwen3ForCausalLM driven one token at
+ * a time by the reference's _forward_pass, acestep/llm_inference.py:416-438) on a causal
+ * handle (every sliding[l] == 2, no embed Linear needed, no proj_out).
+ *
+ * acehip_enc_kv_create allocates, once, the per-layer K / V caches
+ * [layers][max_B][kv_heads][capacity][128] and the partials workspace of the decode
+ * attention; acehip_enc_destroy frees them.  capacity <= cfg.max_S (the RoPE table),
+ * max_B <= cfg.max_tokens.  heads / kv_heads must be 1 or 2 (the prefill runs on the flash
+ * kernels): the 0.6B and 1.7B LMs; ACEHIP_E_ARG otherwise. */
+int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity);
+/* First call of a generation: model(input_ids[B,S], attention_mask[B,S], use_cache=True).
+ * The layer loop of acehip_enc_forward, causal AND key-padded when kmask (device uint8
+ * [B, S], 1 = attend; the batch is left-padded) is given; each layer's K (after norm and
+ * RoPE) and V of positions [0, S) also land in the cache; out bf16 [B, hidden] is the
+ * final-norm row of position S - 1 of every sequence.  B <= max_B, S <= capacity,
+ * B*S <= cfg.max_tokens.  Rows at padded positions stay finite. */
+int acehip_enc_prefill(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream);
+/* Every later call: model(input_ids[:, -1:], past_key_values, attention_mask[B, pos+1]).
+ * x bf16 [B, hidden], one token per sequence at cache index pos = the number of positions
+ * already cached (the same for every row of a left-padded batch); RoPE position = pos, padding
+ * included, as transformers computes it when no position_ids are passed.  kmask: device uint8
+ * [B, mask_ld >= pos + 1] over cache positions, or NULL.  out bf16 [B, hidden] (final norm).
+ * ACEHIP_E_ARG when pos >= capacity.  Caller's stream, no allocation, no host sync. */
+int acehip_enc_decode(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int B, int pos, void *out,
+                      void *stream);
+
 /* FSQ quantizer of the audio tokenizer (ResidualFSQ, 1 quantizer, levels
  * {8,8,8,5,5,5}: base:1196-1200; vector_quantize_pytorch FSQ restated, see
  * oracle/condenc_oracle.py): z bf16 [M, ldz] (the project_in output, first
@@ -428,6 +455,24 @@ int acehip_attention_masked_bf16(const void *q, const void *k, const void *v, vo
 int acehip_attention_probs_bf16(const void *q, const void *k, int B, int H, int KV, int Sq, int Sk,
                                 const int *heads /*host, n*/, int n, int k0, int k1, float scale,
                                 float *out /* [n][B][k1-k0][Sq] */, void *stream);
+
+/* Single-token attention over a K/V cache, head_dim 128, GQA with H/KV in {1, 2, 4} (the
+ * kernel behind acehip_enc_decode): q bf16 [B, H, 128]; k, v bf16 [B, KV, cap, 128] of which
+ * rows [0, n) are valid (n <= cap); kmask uint8 [B, mask_ld >= n] (1 = attend) or NULL.
+ *   o[b][h·128 + :] = Σ_j softmax_j(scale · q[b,h] · k[b, h/(H/KV), j]) · v[b, h/(H/KV), j]
+ * over keys j < n with kmask[b][j] != 0; rows that are masked or past n are never used,
+ * whatever they hold.  A row with no admissible key gives zeros.  ws: device scratch of
+ * acehip_attention_decode_ws_bytes(B, H) bytes (key ranges are folded through it in range
+ * order: bit-identical results from call to call) or NULL (one range per KV head). */
+size_t acehip_attention_decode_ws_bytes(int B, int H);
+int acehip_attention_decode_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV, int n,
+                                 int cap, const uint8_t *kmask, int mask_ld, float scale, void *ws, size_t ws_bytes,
+                                 void *stream);
+
+/* Vocabulary projection of the token loop (lm_head of a bf16 Qwen3ForCausalLM):
+ * y[m][n] = bf16(Σ_k x[m][k] · W[n][k]), fp32 accumulate; M <= 16, any N, K % 8 == 0,
+ * ldx % 8 == 0. */
+int acehip_lm_head_bf16(const void *x, int ldx, const void *W, void *y, int ldy, int M, int N, int K, void *stream);
 
 /* Qwen3RMSNorm (+ AdaLN modulation when shift/scale are given) over rows of D
  * (transformers modeling_qwen3.py:59-64; reference base:499,530,1496):
