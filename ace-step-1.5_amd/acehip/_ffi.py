@@ -160,14 +160,15 @@ def lib():
                                f"{ABI_VERSION} (include/acehip.h); rebuild the library")
         built, tree = build_hash(handle), source_hash()
         if tree is not None and built != tree:
-            raise RuntimeError(f"acehip: {LIB_PATH} was built from native sources {built}, the tree beside "
-                               f"it is {tree}; rebuild the library (make -C ace-step-1.5_amd)")
+            raise RuntimeError(f"acehip: {LIB_PATH} has build hash {built}, the default build of the native "
+                               f"sources beside it is {tree}: {_mismatch_cause(built)}; rebuild the library "
+                               "(make -C ace-step-1.5_amd, no EXTRA)")
         _LIB = handle
     return _LIB
 
 
 def build_hash(handle=None) -> str:
-    """The native-source hash compiled into the library (acehip_build_hash)."""
+    """The build hash compiled into the library (acehip_build_hash): sources + compile flags."""
     h = handle if handle is not None else lib()
     if not hasattr(h, "acehip_build_hash"):
         return "none"
@@ -175,9 +176,8 @@ def build_hash(handle=None) -> str:
     return h.acehip_build_hash().decode()
 
 
-def source_hash():
-    """The native-source hash of the tree this package sits in (None if the sources are absent,
-    e.g. an installed wheel: then only the ABI version is checked)."""
+def _native_hash_module():
+    """csrc/native_hash.py of the tree this package sits in (None if the sources are absent)."""
     script = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc", "native_hash.py")
     if not os.path.exists(script):
         return None
@@ -185,7 +185,29 @@ def source_hash():
     spec = importlib.util.spec_from_file_location("_acehip_native_hash", script)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    return mod.native_hash()
+    return mod
+
+
+def source_hash():
+    """The build hash of the DEFAULT build (gfx950, no extra flags) of the tree this package sits in
+    (None if the sources are absent, e.g. an installed wheel: then only the ABI version is checked)."""
+    mod = _native_hash_module()
+    return mod.native_hash() if mod is not None else None
+
+
+def _mismatch_cause(built: str) -> str:
+    """Why the library's hash is not the default build's: the flags the last `make` recorded
+    (build/flags.stamp) if they explain it, else the sources."""
+    mod = _native_hash_module()
+    stamp = os.path.join(os.path.dirname(os.path.dirname(LIB_PATH)), "build", "flags.stamp")
+    try:
+        flags = dict(ln.split("=", 1) for ln in open(stamp).read().splitlines() if "=" in ln)
+        arch, extra = flags["ARCH"], flags["EXTRA"]
+    except (OSError, KeyError):
+        arch = extra = None
+    if arch is not None and mod.flags_text(arch, extra) != mod.flags_text() and mod.native_hash(arch=arch, extra=extra) == built:
+        return f"it was built with non-default compile flags (ARCH={arch} EXTRA={extra!r})"
+    return "it was built from other native sources or with non-default compile flags (ARCH / EXTRA)"
 
 
 def missing_exports():

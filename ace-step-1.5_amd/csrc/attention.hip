@@ -21,11 +21,10 @@
 // head_post), o token-major [B][Sq][o_ld] at column h·128.
 //
 // Structure: workgroup = the NREP query heads of one KV head (GQA sharing)
-// × 4 waves × 32 queries; KV tiles of 64 keys in a 3-deep LDS ring, the next
+// × 4 waves × 32 queries; KV tiles of 64 keys in a 2-deep LDS ring, the next
 // tile's LDS-DMA (global_load_lds, swizzle applied on the source) in flight
-// during the current tile's MFMAs, one barrier per tile; the
-// second head's waves run P·V one tile late so SIMD partners alternate
-// softmax and MFMA work; tiles are stored as rows of 256 B, 16-B chunks XOR-swizzled so that the
+// during the current tile's MFMAs, one barrier per tile;
+// tiles are stored as rows of 256 B, 16-B chunks XOR-swizzled so that the
 // K row reads (ds_read_b128) and the V transposed reads (ds_read_b64_tr_b16)
 // are bank-conflict free).  Per wave, v_mfma_f32_32x32x16_bf16 computes the
 // swapped score tile Sᵀ = K·Qᵀ, so each lane owns one query row: the row
@@ -45,36 +44,18 @@
 namespace acehip {
 namespace {
 
-#ifndef ATT_XCD
-#define ATT_XCD 1          // XCD-aware block → work-unit remap
-#endif
-#ifndef ATT_DEFER
-#define ATT_DEFER 0        // SIMD partners out of phase: waves 4-7 run each tile's P·V one tile late
-#endif                     // (3-slot ring) — A/B switch: measured 171 → 191 µs (r02), off
-#ifndef ATT_SPLIT_HEADS
-#define ATT_SPLIT_HEADS 1  // GQA pair split into two 4-wave workgroups for short KV loops
-#endif
-// timing experiments only (wrong results; tools/bench_attn.py against the production build):
-// attn_fwd_kernel without the QKᵀ MFMAs, the softmax VALU, the P·V MFMAs, the K/V LDS reads or the
-// per-tile barrier's wait
-#ifndef AF_X_NOQK
-#define AF_X_NOQK 0
-#endif
-#ifndef AF_X_NOSM
-#define AF_X_NOSM 0
-#endif
-#ifndef AF_X_NOPV
-#define AF_X_NOPV 0
-#endif
-#ifndef AF_X_NOREAD
-#define AF_X_NOREAD 0
-#endif
-#ifndef AF_X_NOBAR
-#define AF_X_NOBAR 0
-#endif
-#ifndef ATT_TAU
-#define ATT_TAU 8.0f       // lazy-rescale threshold (0: rescale on every new max)
-#endif
+// Compile-time switches this file once carried (none is left; every line below runs in production):
+//   * ATT_XCD (XCD-aware block → work-unit remap) and ATT_SPLIT_HEADS (GQA pair split into two
+//     4-wave workgroups for short KV loops) were on and are unconditional now.
+//   * ATT_DEFER — tried: SIMD partners out of phase, waves 4-7 of attn_fwd_kernel<2> ran each
+//     tile's P·V one tile late over a 3-slot K/V ring, so that in one barrier interval wave w ran
+//     [QKᵀ(j) | softmax(j) | P·V(j)] while wave w+4 ran [P·V(j−1) | QKᵀ(j) | softmax(j)];
+//     measured 171 → 191 µs (r02), removed.
+//   * AF_X_NOQK / NOSM / NOPV / NOREAD / NOBAR — tried: timing experiments (wrong results by
+//     design) that ran attn_fwd_kernel without the QKᵀ MFMAs, the softmax VALU, the P·V MFMAs,
+//     the K/V LDS reads or the per-tile barrier; each was timed against the production build
+//     with tools/bench_attn.py to size that part of the tile, removed.
+constexpr float ATT_TAU = 8.0f;   // lazy-rescale threshold (0: rescale on every new max)
 
 constexpr int QB = 128;    // queries per workgroup
 constexpr int KT = 64;     // keys per tile
@@ -100,7 +81,6 @@ struct SplitArgs {
     // meet through a last-arriver ticket (cnt[first workgroup], self-resetting) and slabs in ws
     // (2·grid slots); no workgroup waits for another, so residency of the grid is not assumed.
     int sk_total = 0, sk_nt = 0;
-    int prio = 0;           // attn_fwd_kernel<2>: static s_setprio 1 for waves 4-7 (ACEHIP_ATTN_PRIO)
 };
 
 // ds_read_b64_tr_b16 by inline asm (see pv() for why not the builtin)
@@ -122,11 +102,6 @@ __device__ __forceinline__ bf16x8 ds_read_b128(const char *lds_ptr) {
 // block are the instruction's 16-bit offset field (the tile loop is unrolled by the
 // two ring slots so both are constants) — no address VALU per read, and no hoisted
 // VGPR address per (slot, fragment), which had cost ~50 VGPRs and spills.
-__device__ __forceinline__ s16x4 opaque_s16x4() {
-    s16x4 r;
-    asm volatile("" : "=v"(r));
-    return r;
-}
 template <int OFF>
 __device__ __forceinline__ bf16x8 ds_read_b128_imm(uint32_t lane_off) {
     static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
@@ -265,14 +240,13 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
                                                                   const uint8_t *__restrict__ kmask) {
     constexpr int NT = 256 * NREP;
     constexpr int TILE = KT * 256;                 // one K or V tile: 64 rows × 256 B
-    // K/V ring: tile j+1 is staged while tile j is computed; 3 slots when the deferred half
-    // still reads V(j−1) during tile j (deeper rings with more tiles in flight measured
-    // slower on every layer kind, r02: band 53.7 µs at depth 2 vs 56.3 / 56.2 at 3 / 4)
-    constexpr bool DEFER = ATT_DEFER && NREP == 2;
-    constexpr int NBUF = DEFER ? 3 : 2;
+    // K/V ring: tile j+1 is staged while tile j is computed (deeper rings with more tiles in
+    // flight measured slower on every layer kind, r02: band 53.7 µs at depth 2 vs 56.3 / 56.2
+    // at 3 / 4)
+    constexpr int NBUF = 2;
     // [K slot 0 .. NBUF−1 | V slot 0 .. NBUF−1]: the K and the V fragment reads each
     // address their region from their own lane-offset base, so every slot offset fits
-    // the 16-bit ds offset field (3 slots of K|V interleaved would reach 96 KiB)
+    // the 16-bit ds offset field
     __shared__ __attribute__((aligned(16))) char lds[NBUF * 2 * TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
@@ -287,7 +261,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // of the tile sequence, so the units they walk share few K/V heads in that XCD's L2 (with
     // blockIdx.x itself, neighbouring ranges went to different XCDs: L2 hit rate 48 %,
     // profiles/r05v_pmc_tcc.json); slabs and tickets are indexed by the logical number
-    const int cw = (streamk && ATT_XCD) ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int cw = streamk ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     if (streamk) {
         g0 = (int64_t)cw * sp.sk_total / gridDim.x;
         g1 = ((int64_t)cw + 1) * sp.sk_total / gridDim.x;
@@ -301,7 +275,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         pt0 = (int)(g0 % sp.sk_nt);
         pt1 = (int)min<int64_t>(sp.sk_nt, pt0 + (g1 - g0));
     } else {
-        if (ATT_XCD && u < sp.full) u = xcd_remap(u, sp.full);
+        if (u < sp.full) u = xcd_remap(u, sp.full);
         if (u >= sp.full) {
             const int j = u - sp.full;
             u = sp.full + j / sp.nsplit;
@@ -317,9 +291,9 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     const int qblk = qb * QB;
     const int q0 = qblk + (wave & 3) * 32;
     const int qi = q0 + r;
-    // the younger half of the SIMD partners (waves 4-7) gets static priority
-    // (MI355X_MICROARCH.md "Two waves per SIMD", item 4)
-    if (sp.prio && NREP == 2 && __builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1);
+    // (tried: static s_setprio 1 for the younger half of the SIMD partners, waves 4-7 of
+    // attn_fwd_kernel<2> — MI355X_MICROARCH.md "Two waves per SIMD", item 4, ACEHIP_ATTN_PRIO=1:
+    // isolated full attention 170.1 → 165.4 µs, the song neutral (473.2 vs 473.2 ms); removed)
 
     // Q fragments (B operand of Sᵀ = K·Qᵀ): lane holds Q[qi][16s + 8hh .. +8]
     const bf16_t *qp = q + (((int64_t)b * H + hq) * Sq + min(qi, Sq - 1)) * 128;
@@ -402,12 +376,6 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // VB: the V half of the ring slot (compile-time); key rows +32t +16s are immediates too
     auto pv_reads = [&](auto VBC, int dt, s16x4 (&rd)[2][2][2]) {
         constexpr int VB = decltype(VBC)::value;
-        if (AF_X_NOREAD) {
-            for (int a0 = 0; a0 < 2; ++a0)
-                for (int a1 = 0; a1 < 2; ++a1)
-                    for (int a2 = 0; a2 < 2; ++a2) rd[a0][a1][a2] = opaque_s16x4();
-            return;
-        }
         rd[0][0][0] = ds_read_tr16_imm<VB>(voff[dt][0]);
         rd[0][0][1] = ds_read_tr16_imm<VB>(voff[dt][1]);
         rd[0][1][0] = ds_read_tr16_imm<VB + 16 * 256>(voff[dt][0]);
@@ -431,8 +399,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
                 // is miscompiled by ROCm 7.2 hipcc: it keeps only the first dword)
                 const s16x8 cat = __builtin_shufflevector(rd[t][s][0], rd[t][s][1], 0, 1, 2, 3, 4, 5, 6, 7);
                 const bf16x8 vf = __builtin_bit_cast(bf16x8, cat);
-                if (!AF_X_NOPV) oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[t][s], oacc[dt], 0, 0, 0);
-                else oacc[dt][0] += (float)vf[0] + (float)pf[t][s][1];
+                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[t][s], oacc[dt], 0, 0, 0);
             }
     };
     // P·V: the reads of d-block dt+1 are in flight during the MFMAs of dt
@@ -458,39 +425,19 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // vmcnt(0) drain
     auto tile_barrier = [&] {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        if (!AF_X_NOBAR) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
     bf16x8 pf[2][2];          // P of the current tile (bf16), B operand of P·V
 
-    // SIMD partners (wave w and w+4 share a SIMD) are put out of phase: the younger half
-    // defers each tile's P·V into the next tile's interval, so within one barrier interval
-    // wave w runs [QKᵀ(j) | softmax(j) | P·V(j)] while wave w+4 runs [P·V(j−1) | QKᵀ(j) |
-    // softmax(j)]: two of the three segments pair MFMAs with the partner's softmax VALU
-    // instead of both waves issuing the same kind (MI355X_MICROARCH "Two waves per SIMD").
-    // P·V(j−1) precedes softmax(j)'s O rescale, so O is at tile j−1's max when it lands.
-    const bool defer = DEFER && __builtin_amdgcn_readfirstlane(wave) >= 4;
-    bool pending = false;          // deferred half: P of the last computed tile awaits P·V
-    int pend_slot = 0;
-    auto pv_slot = [&](int slot, const bf16x8 (&pfv)[2][2]) {
-        if (slot == 0) pv(IC<0>{}, pfv);
-        else if (slot == 1) pv(IC<TILE>{}, pfv);
-        else pv(IC<2 * TILE>{}, pfv);
-    };
     // one tile; SLOT (compile-time: the loop is unrolled by the ring slots) is the ring
     // slot holding tile it, so every LDS address offset is an immediate
     auto tile = [&](int it, auto SLOTC) {
         constexpr int SLOT = decltype(SLOTC)::value;
         constexpr int KB = SLOT * TILE, VB = SLOT * TILE;    // K from koff, V from voff (region-biased)
-        constexpr int PREV = (SLOT + NBUF - 1) % NBUF;
         const int kv0 = (t_first + it) * KT;
-        // refill: tile it+1 into the slot of tile it+1−NBUF, read by nobody now (with 3
-        // slots that is tile it−2, whose deferred P·V ran in iteration it−1)
+        // refill: tile it+1 into the slot of tile it+1−NBUF, read by nobody now
         if (it + 1 < ntiles) stage_tile(kv0 + KT, (SLOT + 1) % NBUF);
-        if (DEFER && pending) {                     // wave-uniform: the deferred half only
-            pv(IC<PREV * TILE>{}, pf);
-            pending = false;
-        }
         // band layers: a tile entirely outside this wave's |i−j| ≤ window band is
         // skipped (the wave still joins the barrier); one entirely inside needs no mask
         const bool outside = (window >= 0 && !km && (kv0 > q0 + 31 + window || kv0 + KT - 1 < q0 - window)) ||
@@ -510,34 +457,22 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         {
             bf16x8 k0[8], k1[8];
 #pragma unroll
-            for (int s = 0; s < 8; ++s) k0[s] = AF_X_NOREAD ? qf[s] : ds_read_b128_imm<KB>(koff[s]);
+            for (int s = 0; s < 8; ++s) k0[s] = ds_read_b128_imm<KB>(koff[s]);
             lgkm_wait8(k0);
 #pragma unroll
-            for (int s = 0; s < 8; ++s) k1[s] = AF_X_NOREAD ? qf[s] : ds_read_b128_imm<KB + 32 * 256>(koff[s]);
+            for (int s = 0; s < 8; ++s) k1[s] = ds_read_b128_imm<KB + 32 * 256>(koff[s]);
 #pragma unroll
             for (int j = 0; j < 16; ++j) { st[0][j] = 0.f; st[1][j] = 0.f; }
-            if (!AF_X_NOQK) {
 #pragma unroll
-                for (int s = 0; s < 8; ++s) st[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0[s], qf[s], st[0], 0, 0, 0);
-            }
+            for (int s = 0; s < 8; ++s) st[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0[s], qf[s], st[0], 0, 0, 0);
             lgkm_wait8(k1);
-            if (!AF_X_NOQK) {
 #pragma unroll
-                for (int s = 0; s < 8; ++s) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1[s], qf[s], st[1], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int s = 0; s < 8; ++s) {       // keep the reads alive
-                    st[0][s] += (float)k0[s][0];
-                    st[1][s] += (float)k1[s][0];
-                }
-            }
+            for (int s = 0; s < 8; ++s) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1[s], qf[s], st[1], 0, 0, 0);
         }
         // running max on raw scores (scale folded into the exp2 FMA below);
         // interior tiles of full / cross attention need no mask
         float mx = NEG;
-        if (AF_X_NOSM) {
-            mx = m;
-        } else if (interior) {
+        if (interior) {
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -573,7 +508,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                const float p = AF_X_NOSM ? st[t][j] : __builtin_amdgcn_exp2f(fmaf(st[t][j], sl2, -mn));
+                const float p = __builtin_amdgcn_exp2f(fmaf(st[t][j], sl2, -mn));
                 st[t][j] = p;
                 rs += p;
             }
@@ -593,33 +528,17 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
             for (int s = 0; s < 2; ++s)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[t][s][j] = (__bf16)st[t][8 * s + j];
-        if (DEFER && defer) {
-            pending = true;
-            pend_slot = SLOT;
-        } else {
-            pv(IC<VB>{}, pf);
-        }
+        pv(IC<VB>{}, pf);
         tile_barrier();
     };
     if (ntiles > 0) stage_tile(t_first * KT, 0);
     tile_barrier();
     int it = 0;
-    if constexpr (NBUF == 3) {
-        for (; it + 2 < ntiles; it += 3) {
-            tile(it, IC<0>{});
-            tile(it + 1, IC<1>{});
-            tile(it + 2, IC<2>{});
-        }
-        if (it < ntiles) tile(it, IC<0>{});
-        if (it + 1 < ntiles) tile(it + 1, IC<1>{});
-    } else {
-        for (; it + 1 < ntiles; it += 2) {
-            tile(it, IC<0>{});
-            tile(it + 1, IC<1>{});
-        }
-        if (it < ntiles) tile(it, IC<0>{});
+    for (; it + 1 < ntiles; it += 2) {
+        tile(it, IC<0>{});
+        tile(it + 1, IC<1>{});
     }
-    if (DEFER && pending) pv_slot(pend_slot, pf);
+    if (it < ntiles) tile(it, IC<0>{});
 
     if (nsplit > 1) {
         // publish this part's (O, m, l) (slab_store: write-through 16-B stores), then take a
@@ -742,38 +661,14 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
 // Everything that touches them is inline asm, so hipcc neither counts those LDS / global
 // loads (explicit waits) nor pads their hazards (explicit s_nop, noted where used).
 constexpr int PW_O = 0, PW_Q = 128, PW_K = 192;
-// timing experiments only (wrong results): drop the mid-tile barrier / the ring refill /
-// the exponentials / the row max
-#ifndef PW_PV_NOP
-#define PW_PV_NOP 0        // s_nop 1 before every P·V MFMA (else one pf_fence per sub-block)
-#endif
-#ifndef PW_X_NOBAR
-#define PW_X_NOBAR 0
-#endif
-#ifndef PW_X_NODMA
-#define PW_X_NODMA 0
-#endif
-#ifndef PW_X_NOEXP
-#define PW_X_NOEXP 0
-#endif
-#ifndef PW_X_NOMAX
-#define PW_X_NOMAX 0
-#endif
-#ifndef PW_X_NOPV
-#define PW_X_NOPV 0
-#endif
-#ifndef PW_X_NOQK
-#define PW_X_NOQK 0
-#endif
-#ifndef PW_X_NOVREAD
-#define PW_X_NOVREAD 0
-#endif
-#ifndef PW_X_NOKREAD
-#define PW_X_NOKREAD 0
-#endif
-#ifndef PW_X_NOMASK
-#define PW_X_NOMASK 0      // band tiles that straddle the band edge processed unmasked
-#endif
+// Removed compile-time switches of attn_pw_kernel:
+//   * PW_X_NOBAR / NODMA / NOEXP / NOMAX / NOPV / NOQK / NOVREAD / NOKREAD / NOMASK — tried: timing
+//     experiments (wrong results by design) that dropped the mid-tile barrier, the ring refill, the
+//     exponentials, the row max, the P·V or QKᵀ MFMAs, the Vᵀ or K LDS reads, or processed the band
+//     tiles that straddle the band edge unmasked; each was timed against the production build to
+//     size that part of the tile, removed.
+//   * PW_PV_NOP — tried: s_nop 1 before every P·V MFMA in place of one pf_fence per sub-block;
+//     the fence was kept, the other arm removed.
 
 // compile-time loop: f(IC<I>{}) for I in [I0, I1)
 template <int I0, int I1, typename F>
@@ -836,10 +731,6 @@ __device__ __forceinline__ void exp2_pair(float &s0, float &s1, float c, float n
 // ≥ 2 MFMAs later or behind xdl_pad)
 template <int S, int KA, int QA>
 __device__ __forceinline__ void pw_qk(f32x16 &st) {
-#if PW_X_NOQK
-    if constexpr (S == 0) asm volatile("" : "=v"(st));
-    return;
-#endif
     if constexpr (S == 0)
         asm volatile("v_mfma_f32_32x32x16_bf16 %0, a[%c1:%c2], a[%c3:%c4], 0"
                      : "=v"(st) : "n"(KA), "n"(KA + 3), "n"(QA), "n"(QA + 3));
@@ -851,16 +742,7 @@ __device__ __forceinline__ void pw_qk(f32x16 &st) {
 // results the asm cannot see
 template <int OA>
 __device__ __forceinline__ void pw_pv(const bf16x8 &vf, const bf16x8 &pf) {
-#if PW_X_NOPV
-    asm volatile("" :: "v"(vf), "v"(pf));
-    return;
-#endif
-#if PW_PV_NOP
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 a[%c0:%c1], %2, %3, a[%c0:%c1]"
-                 :: "n"(OA), "n"(OA + 15), "v"(vf), "v"(pf));
-#else
     asm volatile("v_mfma_f32_32x32x16_bf16 a[%c0:%c1], %2, %3, a[%c0:%c1]" :: "n"(OA), "n"(OA + 15), "v"(vf), "v"(pf));
-#endif
 }
 // P of one sub-block complete (all its bf16 converts above this point) and past the VALU
 // write → MFMA read hazard before its P·V starts
@@ -870,9 +752,6 @@ __device__ __forceinline__ void pf_fence(bf16x8 (&pf)[2][2]) {
 template <int KA, int OFF>
 __device__ __forceinline__ void pw_kread(uint32_t lane_off) {
     static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-#if PW_X_NOKREAD
-    return;
-#endif
     asm volatile("ds_read_b128 a[%c0:%c1], %2 offset:%c3" :: "n"(KA), "n"(KA + 3), "v"(lane_off), "n"(OFF));
 }
 // XDL (8 passes) → VALU read of its result: 12 wait states
@@ -942,7 +821,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
     const bool persist = sp.units > 0;
     int u = blockIdx.x, part = 0, nsplit = 1;
     if (!persist) {
-        if (ATT_XCD && u < sp.full) u = xcd_remap(u, sp.full);
+        if (u < sp.full) u = xcd_remap(u, sp.full);
         if (u >= sp.full) {
             const int j = u - sp.full;
             u = sp.full + j / sp.nsplit;
@@ -1096,11 +975,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
         auto v_read = [&](auto SLOTC, auto IC_) __attribute__((always_inline)) {
             constexpr int VB = decltype(SLOTC)::value * TILE, i = decltype(IC_)::value;
             constexpr int dt = i >> 3, t = (i >> 2) & 1, s = (i >> 1) & 1, h8 = i & 1;
-#if PW_X_NOVREAD
-            rv[dt][t][s][h8] = opaque_s16x4();
-#else
             rv[dt][t][s][h8] = ds_read_tr16_imm<VB + (32 * t + 16 * s) * 256>(voff[dt][h8]);
-#endif
         };
         auto v_wait = [&] __attribute__((always_inline)) {
     #pragma unroll
@@ -1131,7 +1006,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
             constexpr int sb = decltype(SBC)::value, t = decltype(TC)::value, j0 = decltype(J0C)::value;
             pin(mx[sb]);
             pin(mx2[sb]);
-            if constexpr (decltype(MASKC)::value && !PW_X_NOMASK) {
+            if constexpr (decltype(MASKC)::value) {
                 // key kv0 + c (c = 32t + (j&3) + 8(j>>2) + 4hh) is admissible iff c ∈ [lo, hi]
                 const int lo = (window >= 0 ? qi[sb] - window : -0x40000000) - kv0 - 4 * hh;
                 const int hi = min(window >= 0 ? qi[sb] + window : 0x3fffffff, Sk - 1) - kv0 - 4 * hh;
@@ -1146,11 +1021,9 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
             }
     #pragma unroll
             for (int j = j0; j < j0 + 8; j += 4) {
-#if !PW_X_NOMAX
-            mx[sb] = vmax3(mx[sb], st[sb][t][j], st[sb][t][j + 1]);
-            mx2[sb] = vmax3(mx2[sb], st[sb][t][j + 2], st[sb][t][j + 3]);
-#endif
-        }
+                mx[sb] = vmax3(mx[sb], st[sb][t][j], st[sb][t][j + 1]);
+                mx2[sb] = vmax3(mx2[sb], st[sb][t][j + 2], st[sb][t][j + 3]);
+            }
         };
         // row max over the lane pair, the lazy-rescale reference max and its factor
         auto max_finish = [&](auto SBC) __attribute__((always_inline)) {
@@ -1170,9 +1043,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
             pin(rs[sb]);
             pin(rs2[sb]);
             float s0 = st[sb][t][j0], s1 = st[sb][t][j0 + 1];
-#if !PW_X_NOEXP
             exp2_pair(s0, s1, sl2, -mn[sb], rs[sb], rs2[sb]);
-#endif
             st[sb][t][j0] = s0;
             st[sb][t][j0 + 1] = s1;
         };
@@ -1220,9 +1091,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
             max_finish(IC<1>{});
             v_wait();
         }
-#if !PW_X_NOBAR
         tile_barrier();
-#endif
         if (has_next && it == c_nt - 1) {
             // the next unit's Q, behind the barrier that follows this unit's last QKᵀ MFMAs
             // (s_nop: their AGPR reads before the loads' writes); it lands during this tile's
@@ -1230,10 +1099,8 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
             asm volatile("s_nop 7" ::: "memory");
             load_q(geom(un, 0, 1));
         }
-#if !PW_X_NODMA
         if (it + 2 < c_nt) stage_tile(kv_src, kv0 + 2 * KT, SLOT);
         else if (has_next && it + 2 - c_nt < n_nt) stage_tile(nx_src, (n_tf + it + 2 - c_nt) * KT, SLOT);
-#endif
         const bool more = it + 1 < c_nt || has_next;
         if (!outside) {
             pf_fence(pf[0]);
@@ -1722,12 +1589,16 @@ static int num_cus_attn() {
 }
 
 // short-sequence KV split (a grid of a few units, e.g. the 10 s song's cross-attention: 8
-// units): KV tiles per part.  ACEHIP_ATTN_SHORT_TPP (A/B).  Turbo 10 s cross
+// units): KV tiles per part.  Turbo 10 s cross
 // (11 tiles, 8 units; tools/gpu_r03z.sh, one process): 1 tile per part 28.5 µs, 2: 22.7, 3: 20.3
 // (DiT song 27.7 / 27.1 / 26.8 ms) — fewer, longer parts pay fewer hand-offs; 4 and 6 tiles
 // (after the slab hand-off, tools/gpu_r03m2.sh): 19.6 / 21.9 vs 19.7 µs, song 25.7 / 26.1 vs 25.6
-// ms; default 3
-static int short_tpp() { return knobs().attn_short_tpp; }
+// ms; 3 kept
+constexpr int SHORT_TPP = 3;
+// shortest KV loop (tiles) whose tail units are split on attn_pw_kernel: 24 keeps the 240 s band
+// layers (7 tiles) on the persistent walk (tried 7, the tail split: band 48.8 → 57.0 µs, DiT song
+// 490.9 → 493.8 ms, profiles/r06za_band_tailsplit_ab.log)
+constexpr int PW_SPLIT_MIN = 24;
 
 size_t attention_ws_bytes() {
     const size_t cus = std::max<size_t>(1024, (size_t)num_cus_attn());
@@ -1789,13 +1660,12 @@ int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int 
         const int units = nq * KV * B;
         SplitArgs sp{nq, units, 1, nullptr, nullptr};
         const int tail = units % cus;
-        const int split_min = kn.attn_pw_split;   // shortest KV loop (tiles) whose tail units are split
-        if (ws && unit_tiles >= split_min && units > cus && tail > 0 && tail <= cus / 2) {
+        if (ws && unit_tiles >= PW_SPLIT_MIN && units > cus && tail > 0 && tail <= cus / 2) {
             sp.full = units - tail;
             sp.nsplit = min(4, cus / tail);
         } else if (ws && window < 0 && units * 2 <= cus && unit_tiles >= 4) {
             sp.full = 0;
-            sp.nsplit = min(min(cus / units, (unit_tiles + short_tpp() - 1) / short_tpp()), 16);
+            sp.nsplit = min(min(cus / units, (unit_tiles + SHORT_TPP - 1) / SHORT_TPP), 16);
         }
         if (sp.nsplit > 1) {
             sp.cnt = (int *)ws;
@@ -1814,7 +1684,7 @@ int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int 
         return 0;
     }
     const bool short_split = window < 0 && nq * KV * B * 2 <= cus && unit_tiles >= 4;
-    const bool split_heads = ATT_SPLIT_HEADS && grp == 2 && window != ATTN_CAUSAL &&
+    const bool split_heads = grp == 2 && window != ATTN_CAUSAL &&
                              unit_tiles < 24 && !short_split && nq * KV * B > cus;
     const int nrep = split_heads ? 1 : grp;
     const int units = nq * KV * (grp / nrep) * B;
@@ -1837,7 +1707,7 @@ int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int 
         // short sequences (a few query blocks): every unit split over KV ranges so the
         // grid reaches the CUs (cross-attention of a 10 s song: 8 units → 40 parts)
         sp.full = 0;
-        sp.nsplit = min(min(cus / units, (unit_tiles + short_tpp() - 1) / short_tpp()), 16);
+        sp.nsplit = min(min(cus / units, (unit_tiles + SHORT_TPP - 1) / SHORT_TPP), 16);
         sp.cnt = (int *)ws;
         sp.ws = (float *)((char *)ws + (size_t)std::max(1024, cus) * sizeof(int));
     }
@@ -1859,7 +1729,6 @@ int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int 
         sp.ws = (float *)((char *)ws + wcus * sizeof(int));
         grid = cus;
     }
-    sp.prio = kn.attn_prio;
     if (nrep == 2) {
         attn_fwd_kernel<2><<<grid, 512, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, window, sl2, o_ld, sp, kmask);
     } else if (nrep == 1) {

@@ -566,9 +566,7 @@ struct Conv7 {
     static constexpr int PW = BN / 8 / NW;                   // W pieces per wave (2 / 4)
     static_assert(PWIN * 8 * NW == WROWS && PW * 8 * NW == BN, "pieces split evenly over the waves");
 };
-#ifndef CONV7_BM
-#define CONV7_BM 128
-#endif
+constexpr int CONV7_BM = 128;      // rows per block of the conv7_kernel launches below
 __device__ __forceinline__ int sw7(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
 template <int BM_, bool FUSED, bool RAW>
@@ -1196,35 +1194,27 @@ __device__ __forceinline__ void ru8_w(const ResUnitArgs &u, uint32_t slot, int k
     }
 }
 
-// timing experiments only (wrong results): epilogue 2 without the next Snake / without the
-// snaked store when the raw one is kept
-#ifndef RU8_X_NOSNAKE2
-#define RU8_X_NOSNAKE2 0
-#endif
-#ifndef RU8_X_NOSTORE_S
-#define RU8_X_NOSTORE_S 0
-#endif
-#ifndef RU8_X_NOLOADX
-#define RU8_X_NOLOADX 0    // the residual rows not loaded (zeros): what their re-read from beyond L2 costs
-#endif
-// SIN window rows: loaded RU8_WLEAD helper steps before their Snake + LDS write (2: the rows come
-// from HBM — the previous unit's output — and one step, ≈ 0.6 µs, left the helpers waiting on
-// them at most barriers; 1: the previous schedule, A/B).  Deadlines with lead 2: chunk 1 of a tile
+// Removed compile-time switches of ru8_kernel (every line of it runs in production now):
+//   * RU8_X_NOSNAKE2 / RU8_X_NOSTORE_S / RU8_X_NOLOADX — tried: timing experiments (wrong results
+//     by design): epilogue 2 without the next Snake, without the snaked store when the raw one is
+//     kept, and with the residual rows not loaded (zeros: what their re-read from beyond L2
+//     costs); each was timed against the production build, removed.
+//   * RU8_WPACKED — tried: the window helpers' Snake in packed f32 (v_pk_mul / v_pk_fma); the
+//     helpers issue beside an MFMA wave on their SIMD, where the guide prices packed f32 VALU as
+//     an anti-lever; scalar kept, removed.
+//   * RU8_WLEAD == 1 — tried: the window rows finished one helper step after their loads (the
+//     schedule before lead 2); one step, ≈ 0.6 µs, left the helpers waiting on the rows at most
+//     barriers; removed.
+//   * RU8_NWH == 2 — tried: two window helpers instead of three (see NWH below), removed.
+// SIN window rows: loaded RU8_WLEAD helper steps before their Snake + LDS write (the rows come
+// from HBM — the previous unit's output).  Deadlines with lead 2: chunk 1 of a tile
 // written by step 5 (read from K-tile 7), chunk 0 of the next by step 14 (read from K-tile 0'),
 // the first part of its chunk 1 at steps 0' / 1' (buffer 1 free since K-tile 13)
-#ifndef RU8_WLEAD
-#define RU8_WLEAD 2
-#endif
-// window helpers' Snake in packed f32 (v_pk_mul / v_pk_fma) or scalar: the helpers issue beside
-// an MFMA wave on their SIMD, where the guide prices packed f32 VALU as an anti-lever
-#ifndef RU8_WPACKED
-#define RU8_WPACKED 0
-#endif
+constexpr int RU8_WLEAD = 2;
+static_assert(RU8_WLEAD == 2, "the window helpers' schedule below is written for a lead of two steps");
 // residual prefetch distance in row fragments: fragment i's x rows are loaded while fragment
 // i − RU8_XDIST is in epilogue 2 (the first RU8_XDIST during K-tile 15)
-#ifndef RU8_XDIST
-#define RU8_XDIST 2
-#endif
+constexpr int RU8_XDIST = 2;
 // RU8_STAMPS (diagnostic builds only, tools/ru8_stamps.py): shader-clock stamps of each block's
 // second tile (steady state).  Role 0, MFMA wave 0: before / after every K-tile barrier (slots
 // 2kt, 2kt+1), after the K loop (32), after epilogue 2 (33), real time at the tile's first
@@ -1263,13 +1253,10 @@ __device__ __forceinline__ unsigned long long ru8_now() {
 
 // SIN window helpers: RU8_NWH waves (one per SIMD beside its MFMA wave with the W helper on the
 // fourth; the stamps showed two helpers' Snake VALU arriving 700-1450 cycles after the MFMA waves
-// at most K-tile barriers).  RU8_NWH=2 (A/B): the previous two.
-#ifndef RU8_NWH
-#define RU8_NWH 3
-#endif
+// at most K-tile barriers; the two-helper form is removed).
+constexpr int RU8_NWH = 3;
 namespace ru8 {
 constexpr int NWH = RU8_NWH;
-static_assert(NWH == 2 || NWH == 3, "window helpers");
 }  // namespace ru8
 // SIN window helper H (pieces q ≡ H mod NWH): global 16-B loads of raw x into registers,
 // Snake (the unit's first, sa_in / sib_in), bf16, LDS — the same image the LDS-DMA would write
@@ -1302,12 +1289,8 @@ __device__ __forceinline__ void sin_write(char *buf, uint32_t loff, int l3, cons
         if (q * 8 + 8 <= ru8::WROWS || l3 < ru8::WROWS - q * 8) {
             float x[8], y[8];
             unpack8(ld[k], x);
-            if (RU8_WPACKED) {
-                snake_n<8>(x, sa, sb, y);
-            } else {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) y[e] = snake1(x[e], sa[e], sb[e]);
-            }
+            for (int e = 0; e < 8; ++e) y[e] = snake1(x[e], sa[e], sb[e]);
             *(uint4 *)(buf + q * 1024 + loff) = pack8(y);
         }
         ++k;
@@ -1365,7 +1348,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
         return;
     }
     if (SIN && wave >= 5) {
-        // ---- SIN: two window helpers (raw x → Snake → LDS) ----
+        // ---- SIN: the three window helpers (raw x → Snake → LDS) ----
         auto run = [&](auto HC) __attribute__((always_inline)) {
             constexpr int H = decltype(HC)::value;
             const int l3 = lane >> 3, c = (lane & 7) ^ l3;
@@ -1400,7 +1383,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                 const int64_t m0 = t * RBM;
                 const bool first = t == t0, more = t + 1 < t1;
                 sfor<0, 16>([&](auto KT) __attribute__((always_inline)) {
-                    constexpr int kt = decltype(KT)::value, PB = kt & 1, PP = PB ^ 1;
+                    constexpr int kt = decltype(KT)::value, PB = kt & 1;
                     if (H == 0 && t == t0 + 1) RU8_STAMP(2, 2 * kt, ru8_now());
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's LDS writes landed
                     if (H == 0 && t == t0 + 1) RU8_STAMP(2, 2 * kt + 1, ru8_now());
@@ -1410,16 +1393,14 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                         constexpr int p0 = decltype(P0C)::value, p1 = decltype(P1C)::value, cc = decltype(CCC)::value;
                         sin_write<H, p0, p1>(win + cc * WINB, loff, l3, ld[decltype(BC)::value], sa[cc], sb[cc]);
                     };
-                    if constexpr (RU8_WLEAD == 2) {
-                        // finish step kt − 2's pieces (Snake, LDS) first: they sit in ld[PB], the
-                        // registers step kt issues into next — two steps for their rows to arrive
-                        if constexpr (kt >= 2 && kt <= 5) {          // chunk 1 of this tile
-                            if (!first) fin(IC7<ru8::c1b_lo(kt - 2)>{}, IC7<ru8::c1b_hi(kt - 2)>{}, IC7<1>{}, IC7<PB>{});
-                        } else if constexpr (kt >= 9 && kt <= 14) {  // chunk 0 of the next tile
-                            if (more) fin(IC7<ru8::c0_lo(kt - 9)>{}, IC7<ru8::c0_hi(kt - 9)>{}, IC7<0>{}, IC7<PB>{});
-                        } else if constexpr (kt <= 1) {              // issued at steps 14 / 15 of the previous tile
-                            if (!first) fin(IC7<ru8::c1a_lo(kt)>{}, IC7<ru8::c1a_hi(kt)>{}, IC7<1>{}, IC7<PB>{});
-                        }
+                    // finish step kt − 2's pieces (Snake, LDS) first: they sit in ld[PB], the
+                    // registers step kt issues into next — two steps for their rows to arrive
+                    if constexpr (kt >= 2 && kt <= 5) {          // chunk 1 of this tile
+                        if (!first) fin(IC7<ru8::c1b_lo(kt - 2)>{}, IC7<ru8::c1b_hi(kt - 2)>{}, IC7<1>{}, IC7<PB>{});
+                    } else if constexpr (kt >= 9 && kt <= 14) {  // chunk 0 of the next tile
+                        if (more) fin(IC7<ru8::c0_lo(kt - 9)>{}, IC7<ru8::c0_hi(kt - 9)>{}, IC7<0>{}, IC7<PB>{});
+                    } else if constexpr (kt <= 1) {              // issued at steps 14 / 15 of the previous tile
+                        if (!first) fin(IC7<ru8::c1a_lo(kt)>{}, IC7<ru8::c1a_hi(kt)>{}, IC7<1>{}, IC7<PB>{});
                     }
                     // issue step kt's loads into ld[PB] (the ranges of the DMA schedule)
                     if constexpr (kt <= 3) {
@@ -1429,25 +1410,13 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                     } else if constexpr (kt >= 14) {
                         if (more) sin_issue<H, ru8::c1a_lo(kt - 14), ru8::c1a_hi(kt - 14)>(src_of(m0 + RBM, 1), goff, l3, ld[PB]);
                     }
-                    if constexpr (RU8_WLEAD == 1) {
-                        // finish step kt − 1's pieces (loaded into ld[PP]): Snake, LDS
-                        if constexpr (kt >= 1 && kt <= 4) {          // chunk 1 of this tile, issued at kt − 1
-                            if (!first) fin(IC7<ru8::c1b_lo(kt - 1)>{}, IC7<ru8::c1b_hi(kt - 1)>{}, IC7<1>{}, IC7<PP>{});
-                        } else if constexpr (kt >= 8 && kt <= 13) {  // chunk 0 of the next tile
-                            if (more) fin(IC7<ru8::c0_lo(kt - 8)>{}, IC7<ru8::c0_hi(kt - 8)>{}, IC7<0>{}, IC7<PP>{});
-                        } else if constexpr (kt == 15) {             // chunk 1 (first part) of the next tile
-                            if (more) fin(IC7<ru8::c1a_lo(0)>{}, IC7<ru8::c1a_hi(0)>{}, IC7<1>{}, IC7<PP>{});
-                        } else if constexpr (kt == 0) {              // issued at step 15 of the previous tile
-                            if (!first) fin(IC7<ru8::c1a_lo(1)>{}, IC7<ru8::c1a_hi(1)>{}, IC7<1>{}, IC7<PP>{});
-                        }
-                    }
                 });
             }
             vm_wait<0>();
             if (H == 0) RU8_STAMP_FLUSH(2);
         };
         if (wave == 5) run(IC7<0>{});
-        else if (ru8::NWH == 2 || wave == 6) run(IC7<1>{});
+        else if (wave == 6) run(IC7<1>{});
         else run(IC7<2>{});
         return;
     }
@@ -1544,7 +1513,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
             for (int jp = 0; jp < 4; ++jp) {
                 const int r = (int)min((int64_t)(64 * wave + 16 * i + fr), a.M - 1 - mx);
                 const uint32_t off = (uint32_t)(r * 128 + (2 * jp + (odd ? 1 : 0)) * 16 + (fc >> 1) * 8) * 2;
-                xv[i][jp] = RU8_X_NOLOADX ? u32x4{0u, 0u, 0u, 0u} : *(const u32x4 *)(xb + off);
+                xv[i][jp] = *(const u32x4 *)(xb + off);
             }
         };
 #ifdef RU8_STAMPS
@@ -1677,14 +1646,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                 rbf_n<8>(o);
                 add_n<8>(o, rr);
                 rbf_n<8>(o);
-                if constexpr (!(SIN && RAW)) {
-                    if (RU8_X_NOSNAKE2) {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) sn[r] = o[r];
-                    } else {
-                        snake_n<8>(o, av, sv, sn);
-                    }
-                }
+                if constexpr (!(SIN && RAW)) snake_n<8>(o, av, sv, sn);
                 const int64_t m = me + 64 * wave + 16 * i + fr;
                 if (m < a.M) {
                     if constexpr (SIN) {
@@ -1694,7 +1656,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                         else *(uint4 *)(u.out_s + m * 128 + n) = pack8(sn);
                     } else {
                         if constexpr (RAW) *(uint4 *)(u.x + m * 128 + n) = pack8(o);
-                        if (!(RAW && RU8_X_NOSTORE_S)) *(uint4 *)(u.out_s + m * 128 + n) = pack8(sn);
+                        *(uint4 *)(u.out_s + m * 128 + n) = pack8(sn);
                     }
                 }
             }

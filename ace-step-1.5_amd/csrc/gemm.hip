@@ -758,7 +758,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
 // The tail-split GEMM (gemm_tail_split: whole rounds of 256-row tiles + the remaining rows as
 // one round of 128-row tiles) in ONE launch: blocks [0, nmain) run the main grid, the rest the
 // tail grid, so the tail's blocks start on CUs as the main grid's last round drains instead of
-// behind a kernel boundary (ACEHIP_GEMM_TAILFUSE)
+// behind a kernel boundary
 template <int EPI>
 __global__ __launch_bounds__(512, 1) void gemm_pp_split_kernel(GemmArgs a, GemmArgs t, int nmain) {
     __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<256>()];
@@ -1084,9 +1084,9 @@ static int num_cus() {
 // Half-chip grids (M ≈ 3000: the conditional rows' cross-Q / cross-O): the four-wave
 // 192×128 tile with a 3-deep ring fills the chip in one round (16 × 16 tiles at
 // N = 2048) where the 128² tile runs 0.75 of a 2-blocks-per-CU round: 34–35 → 31 µs,
-// hot or cold weights (tools/bench_gemm.py, r02).  ACEHIP_GEMM_W4S=0 disables it.
+// hot or cold weights (tools/bench_gemm.py, r02).
 static bool use_w4s(int64_t M, int N) {
-    if (knobs().gemm_w4s != 1 || N % 128) return false;
+    if (N % 128) return false;
     const int cus = num_cus();
     const int64_t t = ((M + 191) / 192) * (N / 128);
     return t <= cus && t * 4 >= (int64_t)cus * 3;
@@ -1105,9 +1105,9 @@ int gemm_pick_variant(int64_t M, int N) {
     const int64_t t7 = ((M + 255) / 256) * (N / 256), t8 = ((M + 191) / 192) * (N / 256);
     if (t8 <= cus / 2) return 0;
     // one partial round of 192-row tiles (M ≈ 500: the 20 s song's CFG batch, the lyric
-    // encoder's SwiGLU): 128-row tiles still fit one round and finish sooner (ACEHIP_GEMM_PP128)
+    // encoder's SwiGLU): 128-row tiles still fit one round and finish sooner
     const int64_t t9 = ((M + 127) / 128) * (N / 256);
-    if (knobs().gemm_pp128 && t8 <= cus && t9 <= cus) return 9;
+    if (t8 <= cus && t9 <= cus) return 9;
     const double c7 = (double)((t7 + cus - 1) / cus) * 1.093, c8 = (double)((t8 + cus - 1) / cus);
     return c7 < c8 ? 7 : 8;
 }
@@ -1200,8 +1200,10 @@ static int splitk_finish(const GemmArgs &a, const GemmArgs &p, int splits, hipSt
 // (SwiGLU gate/up at 240 s: 24 × 48 = 1152 tiles of 256² on 256 CUs = 4.5 rounds, the
 // last half-round costing a whole tile time): rows [0, M1) keep the big tile with
 // M1 chosen so their grid is whole rounds (less at most one row of tiles), and the
-// remaining rows run as one round of 128×128 tiles (2 blocks/CU).  Row-local
-// epilogues only (store / SwiGLU; the gated residual indexes its batch by row).
+// remaining rows run as one round of 128×256 two-phase ping-pong tiles where they fit one
+// round (variant 9), else of 128×128 tiles (2 blocks/CU, variant 0).  Row-local epilogues
+// only: store, SwiGLU and head-post (whose tail needs the 128×256 tile: the 128×128 one has
+// no head-post epilogue); the gated residual indexes its batch by row.
 // ACEHIP_GEMM_TAILSPLIT=0 disables it.  Returns 1 when not applicable.
 static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
     if (a.epi != EPI_SWIGLU && a.epi != EPI_STORE && a.epi != EPI_HEADPOST) return 1;
@@ -1220,10 +1222,10 @@ static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
     tl.A = a.A + M1 * a.lda;
     if (a.epi == EPI_HEADPOST) tl.hp.m_off += (int)M1;   // C unused: rows scatter by (b, s)
     else tl.C = a.C + M1 * a.ldc;
-    // ACEHIP_GEMM_TAIL=1: the tail as one round of 128×256 two-phase ping-pong tiles
-    const bool pp128 = knobs().gemm_tail == 1 && a.N % 256 == 0 && ((tl.M + 127) / 128) * nN <= cus;
+    // the tail as one round of 128×256 two-phase ping-pong tiles
+    const bool pp128 = a.N % 256 == 0 && ((tl.M + 127) / 128) * nN <= cus;
     if (a.epi == EPI_HEADPOST && !pp128) return 1;   // the 128×128 tail tile has no head-post epilogue
-    if (pp128 && v == 7 && knobs().gemm_tailfuse) {
+    if (pp128 && v == 7) {
         // both grids in one launch (the main grid's block count is a multiple of 8, so the tail
         // blocks' XCD is their own index mod 8, as in a launch of their own)
         const int nmain = (int)(full * cus / nN * nN), ntail = ((tl.M + 127) / 128) * (int)nN;
@@ -1260,10 +1262,10 @@ int gemm_conv(const GemmArgs &a, hipStream_t s) {
     // short activations (a 10 s decode's C = 1024 / 512 blocks: 40 / 118 tiles of 256 rows on
     // 256 CUs): 128-row tiles double the grid, 64-row tiles (80 KB of LDS, 118 VGPRs: two blocks
     // per CU) quadruple it.  10 s decode 2.13 → 1.96 (128) → 1.91 ms (64 below a quarter of the
-    // chip), bit-identical (profiles/r05az_ab_vae_small_tiles.log; ACEHIP_CONV_BM128)
+    // chip), bit-identical (profiles/r05az_ab_vae_small_tiles.log)
     const int64_t t256 = (int64_t)((a.M + 255) / 256) * (a.N / 256);
-    if (knobs().conv_bm128 == 2 && t256 * 4 <= num_cus()) return launch_conv64(a, s);
-    if (knobs().conv_bm128 && t256 * 2 <= num_cus()) return launch_pp<128>(a, s);
+    if (t256 * 4 <= num_cus()) return launch_conv64(a, s);
+    if (t256 * 2 <= num_cus()) return launch_pp<128>(a, s);
     return launch_pp<256>(a, s);
 }
 
@@ -1304,19 +1306,19 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
     }
     if (a.epi == EPI_HEADPOST) {
         // a 192×256 grid that fills at most half the chip (cross-Q of the conditional rows,
-        // M = 3000) runs as 192×128 tiles — one head each — with the same fused epilogue;
-        // ACEHIP_GEMM_HP128=2: those tiles into the staging buffer + the standalone
-        // head_post kernel (the previous path), =0: the 192×256 grid regardless
+        // M = 3000) runs as 192×128 tiles — one head each — with the same fused epilogue; a
+        // small grid outside the four-wave tile's geometry goes through the staging buffer +
+        // the standalone head_post kernel on 128×128 tiles
         const int64_t t192 = (int64_t)((a.M + 191) / 192) * (a.N / 256);
-        const bool small = t192 * 2 <= num_cus() && kn.gemm_hp128 != 0;
-        if (small && use_w4s(a.M, a.N) && kn.gemm_hp128 != 2) return gemm_variant(a, 13, s);
+        const bool small = t192 * 2 <= num_cus();
+        if (small && use_w4s(a.M, a.N)) return gemm_variant(a, 13, s);
         if (small && a.ws && (size_t)a.M * a.N * 2 <= a.ws_bytes) {
             GemmArgs st = a;
             st.epi = EPI_STORE;
             st.bias = nullptr;
             st.C = (bf16_t *)a.ws;
             st.ldc = a.N;
-            int rc = gemm_variant(st, use_w4s(a.M, a.N) ? 13 : 0, s);
+            int rc = gemm_variant(st, 0, s);
             if (rc) return rc;
             HeadPostArgs hh = a.hp;
             hh.src = st.C;

@@ -9,32 +9,23 @@ namespace acehip {
 // acehip_reload_knobs(); gen counts reloads (part of the DiT graph key)
 struct Knobs {
     int gemm_tailsplit = 1;   // ACEHIP_GEMM_TAILSPLIT: 0 off, 1 on
-    int gemm_tail = 1;        // ACEHIP_GEMM_TAIL: tail-split tile (1: 128×256 ping-pong, 0: 128×128)
     int gemm_helpers = 1;     // ACEHIP_GEMM_HELPERS: LDS-DMA helper waves in the half-chip 4-wave tile
-    int gemm_w4s = 1;         // ACEHIP_GEMM_W4S: half-chip grids on the four-wave 192×128 tile
-    int gemm_hp128 = 1;       // ACEHIP_GEMM_HP128: 0 / 2 alternative cross-Q head-post paths
     int splitk_fuse = 1;      // ACEHIP_SPLITK_FUSE: split-K epilogues folded into their consumers
     int splitk_bn = 0;        // ACEHIP_SPLITK_BN: 0 auto, 64 / 128 forced
     int smallm_wholek = 2;    // ACEHIP_SMALLM_WHOLEK: M ≤ 128 SwiGLU on whole-K 128×64 tiles (2: + DMA helper waves, 1: without, 0: split-K)
     int attn_pw = 2;          // ACEHIP_ATTN_PW: layer kinds on attn_pw_kernel (1 full, 2 band, 4 cross)
     int attn_persist = 1;     // ACEHIP_ATTN_PERSIST: persistent band units
-    int attn_pw_split = 24;   // ACEHIP_ATTN_PW_SPLIT: shortest KV loop whose tail units are split
     int attn_small = 1;       // ACEHIP_ATTN_SMALL: few-unit unmasked full / cross attention on attn_small_kernel (1 with KV parts, 2 without, 0 off)
     int attn_small_mask = 1;  // ACEHIP_ATTN_SMALL_MASK: key-padding-masked full attention (condition encoders) on attn_small_kernel too
     int attn_small_causal = 1; // ACEHIP_ATTN_SMALL_CAUSAL: unmasked causal attention (the text encoder) on attn_small_kernel too
-    int attn_short_tpp = 3;   // ACEHIP_ATTN_SHORT_TPP: KV tiles per part of the short split
     int attn_cus = 0;         // ACEHIP_ATTN_CUS: CU count the splits plan for (0: the device's)
     int attn_streamk = 1;     // ACEHIP_ATTN_STREAMK: stream-K rounds for unmasked full / cross layers
     int fuse_rowadd = 1;      // ACEHIP_FUSE_ROWADD: null-row constant added in the MLP norm
     int dit_dedup = 1;        // ACEHIP_DIT_DEDUP: layer-0 CFG row dedup
     int dit_graph = 0;        // ACEHIP_DIT_GRAPH: HIP-graph replay of the forward body
-    int attn_prio = 0;        // ACEHIP_ATTN_PRIO: attn_fwd_kernel<2> waves 4-7 at s_setprio 1 (the guide's static priority)
-    int gemm_pp128 = 1;       // ACEHIP_GEMM_PP128: a one-round 192-row grid whose 128-row grid also fits one round runs on 128-row tiles
-    int gemm_tailfuse = 1;    // ACEHIP_GEMM_TAILFUSE: the tail-split GEMM's main and tail grids in one launch
     int gemm_hp_tail = 1;     // ACEHIP_GEMM_HPTAIL: head-post GEMMs as a tail split (256-row main rounds + a 128-row tail round) where the cost model prefers it
     int convt = 1;            // ACEHIP_CONVT: 1 ConvTranspose (N % 256 == 0, padded input) as an implicit GEMM, 0 conv_gemm_kernel
     int conv7 = 2;            // ACEHIP_CONV7: k = 7 VAE convs — 2 implicit GEMM on the ping-pong tile (C ≥ 256, padded input), 1 halo-staged conv7_kernel
-    int conv_bm128 = 2;       // ACEHIP_CONV_BM128: GEMM convs whose 256-row grid fills ≤ 1/2 of the chip on 128-row tiles, ≤ 1/4 on 64-row (2; 1: 128 only; 0: 256 always)
     int convp = 3;            // ACEHIP_CONVP: 0 none, 1 all, 2 k = 1 convs on convp_kernel, 3 k = 1 convs with N % 256 == 0 on the ping-pong GEMM (the rest on conv_gemm_kernel)
     int ru7 = 2;              // ACEHIP_RU7: C = 128 residual unit — 2 ru8_kernel (256-row tiles), 1 ru7_kernel, 0 conv7
     int vae_snake_in = 1;     // ACEHIP_VAE_SNAKE_IN: C = 128 decoder blocks without x_s tensors (ru8 SIN)

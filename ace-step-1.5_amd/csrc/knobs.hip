@@ -19,21 +19,15 @@ int env_int(const char *name, int dflt) {
 Knobs read_env() {
     Knobs k;
     k.gemm_tailsplit = env_int("ACEHIP_GEMM_TAILSPLIT", 1);
-    k.gemm_tail = env_int("ACEHIP_GEMM_TAIL", 1);
     k.gemm_helpers = env_int("ACEHIP_GEMM_HELPERS", 1);
-    k.gemm_w4s = env_int("ACEHIP_GEMM_W4S", 1);
-    k.gemm_hp128 = env_int("ACEHIP_GEMM_HP128", 1);
     k.splitk_fuse = env_int("ACEHIP_SPLITK_FUSE", 1);
     k.splitk_bn = env_int("ACEHIP_SPLITK_BN", 0);
     k.smallm_wholek = env_int("ACEHIP_SMALLM_WHOLEK", 2);
     k.attn_pw = env_int("ACEHIP_ATTN_PW", 2);
     k.attn_persist = env_int("ACEHIP_ATTN_PERSIST", 1);
-    k.attn_pw_split = env_int("ACEHIP_ATTN_PW_SPLIT", 24);
-    k.attn_short_tpp = env_int("ACEHIP_ATTN_SHORT_TPP", 3);
     k.attn_small = env_int("ACEHIP_ATTN_SMALL", 1);
     k.attn_small_mask = env_int("ACEHIP_ATTN_SMALL_MASK", 1);
     k.attn_small_causal = env_int("ACEHIP_ATTN_SMALL_CAUSAL", 1);
-    if (k.attn_short_tpp <= 0) k.attn_short_tpp = 3;
     k.attn_cus = env_int("ACEHIP_ATTN_CUS", 0);
     k.attn_streamk = env_int("ACEHIP_ATTN_STREAMK", 1);
     k.fuse_rowadd = env_int("ACEHIP_FUSE_ROWADD", 1);
@@ -41,12 +35,8 @@ Knobs read_env() {
     k.dit_graph = env_int("ACEHIP_DIT_GRAPH", 0);
     k.conv7 = env_int("ACEHIP_CONV7", 2);
     k.convt = env_int("ACEHIP_CONVT", 1);
-    k.gemm_tailfuse = env_int("ACEHIP_GEMM_TAILFUSE", 1);
     k.gemm_hp_tail = env_int("ACEHIP_GEMM_HPTAIL", 1);
-    k.gemm_pp128 = env_int("ACEHIP_GEMM_PP128", 1);
-    k.attn_prio = env_int("ACEHIP_ATTN_PRIO", 0);
     k.convp = env_int("ACEHIP_CONVP", 3);
-    k.conv_bm128 = env_int("ACEHIP_CONV_BM128", 2);
     k.ru7 = env_int("ACEHIP_RU7", 2);
     k.kv_group_kib = env_int("ACEHIP_KV_GROUP_KIB", 262144);
     k.vae_snake_in = env_int("ACEHIP_VAE_SNAKE_IN", 1);

@@ -62,9 +62,11 @@ int acehip_get_version(void);
  * library; a DiT handle re-captures its HIP graph after a reload. */
 int acehip_reload_knobs(void);
 const char *acehip_last_error(void);
-/* Content hash of the native sources the library was built from (the .hip and .h files under
- * csrc/ and include/; ace-step-1.5_amd/csrc/native_hash.py).  acehip/_ffi.py refuses a library whose
- * hash differs from the sources beside it, so a shipped binary is provably the tree's. */
+/* Hash of what the library was built from and how: the native sources (the .hip and .h files under
+ * csrc/ and include/), the Makefile and the compile flags `make` received (ARCH, EXTRA);
+ * ace-step-1.5_amd/csrc/native_hash.py.  acehip/_ffi.py refuses a library whose hash differs from the
+ * default build (gfx950, no EXTRA) of the sources beside it, so a shipped binary is provably the
+ * tree's and no diagnostic build. */
 const char *acehip_build_hash(void);
 
 /* ---------------------------------------------------------------- DiT ---- */

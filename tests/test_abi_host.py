@@ -39,6 +39,52 @@ def test_library_built_from_this_tree(monkeypatch):
     assert _ffi.lib() is lib
 
 
+def _makefile_hash(tmp_path, *make_args):
+    """The hash the Makefile would compile in: the -DACEHIP_BUILD_HASH of a dry run (nothing is
+    built; the flags stamp goes to tmp_path, not into the tree)."""
+    import subprocess
+    pkg = os.path.join(REPO, "ace-step-1.5_amd")
+    env = {k: v for k, v in os.environ.items() if k not in ("ARCH", "EXTRA", "MAKEFLAGS", "MFLAGS")}
+    out = subprocess.run(["make", "-C", pkg, "-n", "-B", "build/buildhash.o", f"STAMP={tmp_path}/flags.stamp",
+                          *make_args], check=True, capture_output=True, text=True, env=env).stdout
+    hashes = re.findall(r"-DACEHIP_BUILD_HASH='\"([^\"]*)\"'", out)
+    assert len(hashes) == 1, out
+    return hashes[0]
+
+
+def test_build_hash_covers_compile_flags(tmp_path):
+    """The build hash covers the flags `make` received as well as the sources: a non-empty EXTRA
+    (or another ARCH) gives another hash, which _ffi.lib() therefore refuses, and what the Makefile
+    compiles in is native_hash() of the same flags (for the default build: _ffi.source_hash())."""
+    from acehip import _ffi
+    nh = _ffi._native_hash_module()
+    default = _ffi.source_hash()
+    assert default == nh.native_hash() == nh.native_hash(arch=nh.DEFAULT_ARCH, extra="")
+    stamps = nh.native_hash(extra="-DGEMM_STAMPS")
+    others = {stamps, nh.native_hash(extra="-DRU8_STAMPS"), nh.native_hash(extra="-O1"),
+              nh.native_hash(arch="gfx942"), nh.native_hash(arch="gfx942", extra="-DGEMM_STAMPS")}
+    assert len(others) == 5 and default not in others
+    assert nh.native_hash(extra="  -DGEMM_STAMPS ") == stamps          # as make passes it on, unquoted
+    for h in others | {default}:
+        assert re.fullmatch(r"[0-9a-f]{16}", h)
+    assert _makefile_hash(tmp_path) == default
+    assert _makefile_hash(tmp_path, f"ARCH={nh.DEFAULT_ARCH}", "EXTRA=") == default
+    assert _makefile_hash(tmp_path, "EXTRA=-DGEMM_STAMPS") == stamps
+
+
+def test_flags_stamp_rewritten_only_on_change(tmp_path):
+    """Every object depends on the flags stamp, so it must change when, and only when, the flags do."""
+    from acehip import _ffi
+    nh = _ffi._native_hash_module()
+    stamp = tmp_path / "b" / "flags.stamp"
+    nh.write_stamp(str(stamp), nh.flags_text())
+    os.utime(stamp, ns=(1, 1))
+    nh.write_stamp(str(stamp), nh.flags_text(nh.DEFAULT_ARCH, " "))
+    assert stamp.stat().st_mtime_ns == 1
+    nh.write_stamp(str(stamp), nh.flags_text(extra="-DGEMM_STAMPS"))
+    assert stamp.stat().st_mtime_ns != 1 and stamp.read_text() == "ARCH=gfx950\nEXTRA=-DGEMM_STAMPS\n"
+
+
 def test_error_paths_without_gpu():
     from acehip import _ffi
     lib = _ffi.lib()
