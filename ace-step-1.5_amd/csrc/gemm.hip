@@ -47,18 +47,22 @@ __device__ __forceinline__ void stamp(int slot, int i, unsigned long long v) {
         g_gemm_stamps[slot * 8 + i] = v;
     }
 }
-#define GSTAMP(i)                                                                                \
+// (the ping-pong bodies stamp by tile: slot = the tile's index in the launch's grid, which is
+// blockIdx.x except in the persistent kernel, whose workgroups stamp every tile they walk)
+#define GSTAMP_AT(slot, i)                                                                       \
     do {                                                                                         \
-        if ((threadIdx.x & 255) == 0 && threadIdx.x < 512) stamp(blockIdx.x * 2 + (threadIdx.x >> 8), i, __builtin_amdgcn_s_memtime()); \
+        if ((threadIdx.x & 255) == 0 && threadIdx.x < 512) stamp((slot) * 2 + (threadIdx.x >> 8), i, __builtin_amdgcn_s_memtime()); \
     } while (0)
-#define GSTAMP_REAL(i)                                                                           \
+#define GSTAMP_REAL_AT(slot, i)                                                                  \
     do {                                                                                         \
-        if ((threadIdx.x & 255) == 0 && threadIdx.x < 512) stamp(blockIdx.x * 2 + (threadIdx.x >> 8), i, __builtin_amdgcn_s_memrealtime()); \
+        if ((threadIdx.x & 255) == 0 && threadIdx.x < 512) stamp((slot) * 2 + (threadIdx.x >> 8), i, __builtin_amdgcn_s_memrealtime()); \
     } while (0)
 #else
-#define GSTAMP(i) do {} while (0)
-#define GSTAMP_REAL(i) do {} while (0)
+#define GSTAMP_AT(slot, i) do {} while (0)
+#define GSTAMP_REAL_AT(slot, i) do {} while (0)
 #endif
+#define GSTAMP(i) GSTAMP_AT(blockIdx.x, i)
+#define GSTAMP_REAL(i) GSTAMP_REAL_AT(blockIdx.x, i)
 
 // launch-attached timing events (gemm_ext_events): a hipEventRecord around a launch is its own
 // barrier packet — ≈ 5.6 µs of idle GPU before and after the timed kernel on this stack
@@ -573,17 +577,14 @@ __device__ __forceinline__ void headpost_epilogue(const GemmArgs &a, char *lds, 
 // main + tail launch below runs two GEMMs' grids in one) and `lds` = the kernel's 2·BUF bytes
 template <int BM>
 constexpr int pp_lds_bytes() { return 2 * (BM + 256) * 128; }
-template <int BM, int EPI>
-__device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int bid) {
-    constexpr int BN = 256, TM = BM / 2, SM = TM / 16, SMH = SM / 2;
-    constexpr int ROWS = BM + BN, BUF = ROWS * 128;
-    constexpr int NA = BM / 64, NB = BN / 64;                // glds per wave for A / B of one K-tile
-    static_assert(SM % 2 == 0, "A half must be whole 16-row sub-tiles");
-
-    GSTAMP(0);
-    GSTAMP_REAL(4);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 2, wc = wave & 3;
+//
+// The body is three pieces — pp_tile_origin + a source-address set (where tile `bid` lies and
+// where its operands come from), pp_main (accumulators, prologue, K loop) and pp_epilogue —
+// which the one-tile-per-workgroup kernels call once in that order and the persistent kernel
+// (gemm_pp_persist_kernel) calls per tile, with the next tile's prologue issued in between.
+template <int BM>
+__device__ __forceinline__ void pp_tile_origin(const GemmArgs &a, int bid, int slot, int &m0, int &n0) {
+    constexpr int BN = 256;
     const int tilesM = (a.M + BM - 1) / BM, tilesN = a.N / BN;
     const int nwg = tilesM * tilesN;
     const int wg = xcd_remap(bid, nwg);
@@ -592,52 +593,138 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
     const int gsz = min(tilesM - first_m, GROUP_M);
     const int tm = first_m + (wg % per_group) % gsz;
     const int tn = (wg % per_group) / gsz;
-    const int m0 = tm * BM, n0 = tn * BN;
+    m0 = tm * BM;
+    n0 = tn * BN;
 #ifdef GEMM_STAMPS
     {
         unsigned xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        if ((threadIdx.x & 255) == 0) stamp(blockIdx.x * 2 + (threadIdx.x >> 8), 6, ((unsigned long long)wg << 32) | xcc);
+        if ((threadIdx.x & 255) == 0) {
+            stamp(slot * 2 + (threadIdx.x >> 8), 6, ((unsigned long long)wg << 32) | xcc);
+            stamp(slot * 2 + (threadIdx.x >> 8), 7, blockIdx.x);   // the workgroup that ran the tile
+        }
     }
 #endif
+}
 
-    const bf16_t *srcA[NA], *srcB[NB];
+// Source addresses of a wave's LDS-DMA pieces, one 64-bit pointer per piece and lane (the tile
+// a one-tile workgroup keeps for its whole life)
+template <int BM>
+struct PPSrcPtr {
+    static constexpr int NA = BM / 64, NB = 4;               // glds per wave for A / B of one K-tile
+    const bf16_t *pa[NA], *pb[NB];
+    __device__ __forceinline__ void set(const GemmArgs &a, int m0, int n0, int wave, int lane) {
 #pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int r = (wave + 8 * i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        srcA[i] = a.A + (int64_t)min(m0 + r, a.M - 1) * a.lda + c * 8;
-    }
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const int r = (wave + 8 * i) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ (((BM + r) >> 1) & 7);
-        srcB[i] = a.W + (int64_t)(n0 + r) * a.ldw + c * 8;
-    }
-    auto stageA = [&](int buf, int k0) {
-        char *b = lds + buf * BUF;
-        int ko = k0;
-        if constexpr (EPI == EPI_CONV) {
-            // implicit-GEMM conv: K-tile k0 = tap·cin + c0 reads the input rows shifted by
-            // conv_a0 + tap·dil (zero halo rows around the activation)
-            const int cin = a.conv_cin, tap = k0 / cin;
-            ko = k0 + tap * (a.conv_dil - 1) * cin + a.conv_a0 * cin;
+        for (int i = 0; i < NA; ++i) {
+            const int r = (wave + 8 * i) * 8 + (lane >> 3);
+            const int c = (lane & 7) ^ ((r >> 1) & 7);
+            pa[i] = a.A + (int64_t)min(m0 + r, a.M - 1) * a.lda + c * 8;
         }
 #pragma unroll
-        for (int i = 0; i < NA; ++i) glds16(srcA[i] + ko, b + (wave + 8 * i) * 1024);
-    };
-    auto stageB = [&](int buf, int k0) {
-        char *b = lds + buf * BUF + BM * 128;
-#pragma unroll
-        for (int i = 0; i < NB; ++i) glds16(srcB[i] + k0, b + (wave + 8 * i) * 1024);
-    };
-    auto bar = [] {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
+        for (int i = 0; i < NB; ++i) {
+            const int r = (wave + 8 * i) * 8 + (lane >> 3);
+            const int c = (lane & 7) ^ (((BM + r) >> 1) & 7);
+            pb[i] = a.W + (int64_t)(n0 + r) * a.ldw + c * 8;
+        }
+    }
+    // piece i of the K-tile at element offset k0 → the wave's 1 KiB LDS slot
+    __device__ __forceinline__ void dmaA(int i, int k0, char *dst) const { glds16(pa[i] + k0, dst); }
+    __device__ __forceinline__ void dmaB(int i, int k0, char *dst) const { glds16(pb[i] + k0, dst); }
+};
 
-    f32x4 acc[SM][4];
+// LDS-DMA of one 1 KiB piece in the saddr form (SGPR base, 32-bit per-lane offset), as
+// attention.hip's pw_dma; M0 (the LDS destination) is written in the same statement
+__device__ __forceinline__ void glds16_s(const char *sbase, uint32_t voff, char *lds_dst) {
+    const uint32_t la = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds_dst;
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(la), "v"(voff), "s"(sbase)
+                 : "memory");
+}
+
+// The same addresses as a wave-uniform tile base (scalar registers: the tile origin is the
+// same for every lane) + 32-bit per-lane byte offsets.  A tile walk derives the next tile's set
+// from scalars after the K loop instead of holding a second set of 64-bit pointers across it.
+// The offsets do not depend on the tile — the swizzle chunk (lane & 7) ^ ((r >> 1) & 7) is the
+// same for rows 64 apart — but for the A rows clamped to M − 1, a no-op except on the last row tile.
+template <int BM>
+struct PPSrcOff {
+    static constexpr int NA = BM / 64, NB = 4;
+    const char *ba, *bb;
+    uint32_t oa[NA], ob, bstep;
+    __device__ __forceinline__ void set(const GemmArgs &a, int m0, int n0, int wave, int lane) {
+        ba = (const char *)(a.A + (int64_t)m0 * a.lda);
+        bb = (const char *)(a.W + (int64_t)n0 * a.ldw);
+        bstep = 64u * (uint32_t)a.ldw * 2u;
+        const int r0 = wave * 8 + (lane >> 3);
+        const uint32_t c16 = (uint32_t)((lane & 7) ^ ((r0 >> 1) & 7)) * 16u;
+        ob = (uint32_t)r0 * (uint32_t)a.ldw * 2u + c16;
+        const int last = a.M - 1 - m0;
+#pragma unroll
+        for (int i = 0; i < NA; ++i) oa[i] = (uint32_t)min(r0 + 64 * i, last) * (uint32_t)a.lda * 2u + c16;
+    }
+    __device__ __forceinline__ void dmaA(int i, int k0, char *dst) const { glds16_s(ba + (int64_t)k0 * 2, oa[i], dst); }
+    __device__ __forceinline__ void dmaB(int i, int k0, char *dst) const {
+        glds16_s(bb + (uint64_t)i * bstep + (int64_t)k0 * 2, ob, dst);
+    }
+};
+
+template <int BM, int EPI, typename Src>
+__device__ __forceinline__ void pp_stageA(const GemmArgs &a, char *lds, const Src &src, int wave, int buf, int k0) {
+    constexpr int BUF = (BM + 256) * 128;
+    char *b = lds + buf * BUF;
+    int ko = k0;
+    if constexpr (EPI == EPI_CONV) {
+        // implicit-GEMM conv: K-tile k0 = tap·cin + c0 reads the input rows shifted by
+        // conv_a0 + tap·dil (zero halo rows around the activation)
+        const int cin = a.conv_cin, tap = k0 / cin;
+        ko = k0 + tap * (a.conv_dil - 1) * cin + a.conv_a0 * cin;
+    }
+#pragma unroll
+    for (int i = 0; i < Src::NA; ++i) src.dmaA(i, ko, b + (wave + 8 * i) * 1024);
+}
+template <int BM, typename Src>
+__device__ __forceinline__ void pp_stageB(char *lds, const Src &src, int wave, int buf, int k0) {
+    constexpr int BUF = (BM + 256) * 128;
+    char *b = lds + buf * BUF + BM * 128;
+#pragma unroll
+    for (int i = 0; i < Src::NB; ++i) src.dmaB(i, k0, b + (wave + 8 * i) * 1024);
+}
+__device__ __forceinline__ void pp_bar() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+// the prologue's LDS-DMAs: tile 0 complete, B(1) in flight
+template <int BM, int EPI, typename Src>
+__device__ __forceinline__ void pp_prologue_issue(const GemmArgs &a, char *lds, const Src &src, int wave) {
+    pp_stageB<BM>(lds, src, wave, 0, 0);
+    pp_stageA<BM, EPI>(a, lds, src, wave, 0, 0);
+    if (a.K > BK) pp_stageB<BM>(lds, src, wave, 1, BK);
+}
+
+// Stores of one wave in the SwiGLU epilogue of a full 256-row tile (one 16-B store per 16-row
+// group): what a persistent workgroup has in flight BEHIND the next tile's prologue DMAs
+constexpr int PP_SWIGLU_STORES = 256 / 2 / 16;
+
+// Accumulators, prologue and K loop of one tile.  `pend` (PERSIST only): −1 the prologue is
+// issued here, as in a one-tile workgroup; otherwise it was issued before the previous tile's
+// epilogue — 1: followed by exactly PP_SWIGLU_STORES stores per wave (vmcnt counts loads and
+// stores together, in order, so the counted wait leaves them and B(1) in flight), 0: by an
+// unknown number of stores (a ragged tile skips some), all waited for.
+template <int BM, int EPI, bool PERSIST, typename Src>
+__device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src &src, f32x4 (&acc)[BM / 32][4],
+                                        int slot, int pend) {
+    constexpr int BN = 256, TM = BM / 2, SM = TM / 16, SMH = SM / 2;
+    constexpr int ROWS = BM + BN, BUF = ROWS * 128;
+    constexpr int NB = BN / 64;
+    static_assert(SM % 2 == 0, "A half must be whole 16-row sub-tiles");
+    const int tid = threadIdx.x, lane = tid & 63;
+    int wave = tid >> 6;
+    if constexpr (PERSIST) wave = __builtin_amdgcn_readfirstlane(wave);   // scalar LDS slot addresses (glds16_s)
+    const int wr = wave >> 2, wc = wave & 3;
+    auto stageA = [&](int buf, int k0) { pp_stageA<BM, EPI>(a, lds, src, wave, buf, k0); };
+    auto stageB = [&](int buf, int k0) { pp_stageB<BM>(lds, src, wave, buf, k0); };
+    auto bar = [] { pp_bar(); };
+
 #pragma unroll
     for (int i = 0; i < SM; ++i)
 #pragma unroll
@@ -647,18 +734,30 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
     const int arow = wr * TM, brow = BM + wc * 64;
 
     const int nk = a.K / BK;
-    // prologue: tile 0 complete, B(1) in flight
-    stageB(0, 0);
-    stageA(0, 0);
-    if (nk > 1) {
-        stageB(1, BK);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
+    if constexpr (!PERSIST) {
+        // prologue: tile 0 complete, B(1) in flight
+        stageB(0, 0);
+        stageA(0, 0);
+        if (nk > 1) {
+            stageB(1, BK);
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (pend < 0) pp_prologue_issue<BM, EPI>(a, lds, src, wave);
+        __builtin_amdgcn_sched_barrier(0);
+        if (pend > 0) {
+            if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB + PP_SWIGLU_STORES) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PP_SWIGLU_STORES) : "memory");
+        } else {
+            if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
     }
     bar();
     if (wr == 1) bar();   // group 1 runs one barrier behind
-    GSTAMP(1);
+    GSTAMP_AT(slot, 1);
 
     {
     bf16x8 xa[SMH][2], bf[4][2];
@@ -708,9 +807,17 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
         bar();
     }
     }
-    if (wr == 0) bar();   // balance the barrier count
-    GSTAMP(2);
+    if (wr == 0) bar();   // balance the barrier count: every wave's LDS reads have retired
+    GSTAMP_AT(slot, 2);
+}
 
+template <int BM, int EPI>
+__device__ __forceinline__ void pp_epilogue(const GemmArgs &a, char *lds, const f32x4 (&acc)[BM / 32][4], int m0, int n0) {
+    constexpr int TM = BM / 2, SM = TM / 16, BUF = (BM + 256) * 128;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 2, wc = wave & 3;
+    const int fr = lane & 15, fc = lane >> 4;
+    const int arow = wr * TM;
     if constexpr (EPI == EPI_HEADPOST && BM == 256) {
         // the 256-row staging tile (135 KB at the padded pitch) exceeds the operand ring: the two
         // wave groups' 128-row halves go through it one after the other (headpost_epilogue's
@@ -742,11 +849,102 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
     }
 
     epilogue_tile<SM, 4, EPI>(a, acc, m0 + arow, n0 + wc * 64, fr, fc);
+}
+
+template <int BM, int EPI>
+__device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int bid) {
+    GSTAMP(0);
+    GSTAMP_REAL(4);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int m0, n0;
+    pp_tile_origin<BM>(a, bid, blockIdx.x, m0, n0);
+    PPSrcPtr<BM> src;
+    src.set(a, m0, n0, wave, lane);
+    f32x4 acc[BM / 32][4];
+    pp_main<BM, EPI, false>(a, lds, src, acc, blockIdx.x, -1);
+    pp_epilogue<BM, EPI>(a, lds, acc, m0, n0);
+    if constexpr (EPI == EPI_HEADPOST) return;
 #ifdef GEMM_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     GSTAMP(3);
     GSTAMP_REAL(5);
+}
+
+// Persistent tile walk (SwiGLU gate/up, whose epilogue writes straight from registers and leaves
+// the operand ring alone): one workgroup per CU, workgroup w takes tiles w, w + G, w + 2G, … of
+// the launch's tile list — the main grid's 256² tiles, then the tail-split tail's 128×256 ones
+// (gemm_tail_split), i.e. the order in which the hardware hands the fused main + tail grid's
+// blocks to the CUs, so xcd_remap + GROUP_M keep their per-XCD panel sharing.  At a tile
+// boundary the ring is idle (every wave's LDS reads retired before the K loop's closing
+// barrier), so the NEXT tile's whole prologue — B(0), A(0), B(1) — is issued before this tile's
+// epilogue and lands under it; the next K loop is entered on a counted vmcnt that leaves B(1) and
+// the epilogue's stores in flight (pp_main).  A one-tile workgroup instead ends, the next is
+// dispatched onto an empty ring, and its prologue waits a full memory latency before the
+// first MFMA.  The next tile's addresses are derived from scalars after the K loop (PPSrcOff).
+// No workgroup waits for another and nothing is kept between launches.
+// The host guarantees ntot − nmain ≤ gridDim.x: a tail tile is its workgroup's last (a tail tile
+// followed by another would still be correct — its prologue is simply not issued early).
+template <int EPI>
+__global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, GemmArgs t, int nmain, int ntot) {
+    static_assert(EPI == EPI_SWIGLU, "the early prologue needs an epilogue that leaves LDS alone and a known store count");
+    __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<256>()];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int G = gridDim.x;
+    int i = blockIdx.x;
+    int pend = -1;   // ≥ 0: tile i's prologue is already in flight (pp_main)
+    int m0 = 0, n0 = 0;
+    GSTAMP_AT(i, 0);
+    GSTAMP_REAL_AT(i, 4);
+    PPSrcOff<256> src;
+    PPSrcOff<128> tsrc;
+    if (i < nmain) {
+        pp_tile_origin<256>(a, i, i, m0, n0);
+        src.set(a, m0, n0, wave, lane);
+    }
+    for (; i < nmain; i += G) {
+        f32x4 acc[8][4];
+        pp_main<256, EPI, true>(a, lds, src, acc, i, pend);
+        const int cm0 = m0, cn0 = n0, nx = i + G;
+        pend = cm0 + 256 <= a.M ? 1 : 0;   // a ragged tile's waves skip stores
+        if (nx < ntot) {
+            GSTAMP_AT(nx, 0);
+            GSTAMP_REAL_AT(nx, 4);
+        }
+        if (nx < nmain) {
+            pp_tile_origin<256>(a, nx, nx, m0, n0);
+            src.set(a, m0, n0, wave, lane);
+            pp_prologue_issue<256, EPI>(a, lds, src, wave);
+        } else if (nx < ntot) {
+            pp_tile_origin<128>(t, nx - nmain, nx, m0, n0);
+            tsrc.set(t, m0, n0, wave, lane);
+            pp_prologue_issue<128, EPI>(t, lds, tsrc, wave);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        pp_epilogue<256, EPI>(a, lds, acc, cm0, cn0);
+        __builtin_amdgcn_sched_barrier(0);
+        GSTAMP_AT(i, 3);
+        GSTAMP_REAL_AT(i, 5);
+    }
+    for (; i < ntot; i += G) {
+        if (pend < 0) {
+            pp_tile_origin<128>(t, i - nmain, i, m0, n0);
+            tsrc.set(t, m0, n0, wave, lane);
+        }
+        f32x4 acc[4][4];
+        pp_main<128, EPI, true>(t, lds, tsrc, acc, i, pend);
+        pend = -1;
+        pp_epilogue<128, EPI>(t, lds, acc, m0, n0);
+#ifdef GEMM_STAMPS
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+        GSTAMP_AT(i, 3);
+        GSTAMP_REAL_AT(i, 5);
+        if (i + G < ntot) {
+            GSTAMP_AT(i + G, 0);
+            GSTAMP_REAL_AT(i + G, 4);
+        }
+    }
 }
 
 template <int BM, int EPI>
@@ -1080,6 +1278,22 @@ static int num_cus() {
     }
     return n;
 }
+// the CU count the tile planner (gemm_pick_variant, gemm_tail_split, the persistent grid) fills:
+// the device's, or fewer under ACEHIP_GEMM_CUS so tests reach multi-round grids at small shapes
+static int plan_cus() {
+    const int cap = knobs().gemm_cus, n = num_cus();
+    return cap > 0 && cap < n ? cap : n;
+}
+
+// The persistent SwiGLU tile walk (gemm_pp_persist_kernel): the main grid's nmain 256² tiles
+// and the tail's ntail 128×256 ones (at most one per workgroup) on one workgroup per planned CU
+static int launch_pp_persist(const GemmArgs &hd, const GemmArgs &tl, int nmain, int ntail, hipStream_t s) {
+    const int grid = std::min(plan_cus(), nmain + ntail);
+    if (ntail > grid) return fail(-1, "gemm: persistent walk with more tail tiles than workgroups");
+    klaunch(gemm_pp_persist_kernel<EPI_SWIGLU>, dim3(grid), dim3(512), s, hd, tl, nmain, nmain + ntail);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 // Half-chip grids (M ≈ 3000: the conditional rows' cross-Q / cross-O): the four-wave
 // 192×128 tile with a 3-deep ring fills the chip in one round (16 × 16 tiles at
@@ -1101,7 +1315,7 @@ static bool use_w4s(int64_t M, int N) {
 int gemm_pick_variant(int64_t M, int N) {
     if (use_w4s(M, N) && (N % 256 || ((M + 191) / 192) * (N / 256) <= num_cus() / 2)) return 13;
     if (N % 256) return 0;
-    const int cus = num_cus();
+    const int cus = plan_cus();
     const int64_t t7 = ((M + 255) / 256) * (N / 256), t8 = ((M + 191) / 192) * (N / 256);
     if (t8 <= cus / 2) return 0;
     // one partial round of 192-row tiles (M ≈ 500: the 20 s song's CFG batch, the lyric
@@ -1208,7 +1422,7 @@ static int splitk_finish(const GemmArgs &a, const GemmArgs &p, int splits, hipSt
 static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
     if (a.epi != EPI_SWIGLU && a.epi != EPI_STORE && a.epi != EPI_HEADPOST) return 1;
     if (!knobs().gemm_tailsplit) return 1;
-    const int BMv = v == 7 ? 256 : 192, cus = num_cus();   // v = 7 or 8
+    const int BMv = v == 7 ? 256 : 192, cus = plan_cus();   // v = 7 or 8
     const int64_t nN = a.N / 256, tiles = (int64_t)((a.M + BMv - 1) / BMv) * nN;
     const int64_t full = tiles / cus, rem = tiles - full * cus;
     if (full < 1 || rem == 0 || rem * 5 > (int64_t)cus * 3) return 1;   // last round > 60 % full
@@ -1229,6 +1443,9 @@ static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
         // both grids in one launch (the main grid's block count is a multiple of 8, so the tail
         // blocks' XCD is their own index mod 8, as in a launch of their own)
         const int nmain = (int)(full * cus / nN * nN), ntail = ((tl.M + 127) / 128) * (int)nN;
+        // SwiGLU: one persistent walk over both grids (ACEHIP_GEMM_PERSIST=0: the launch below)
+        if (a.epi == EPI_SWIGLU && knobs().gemm_persist && nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0)
+            return launch_pp_persist(hd, tl, nmain, ntail, s);
         if (nmain % 8 == 0 && nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0) {
             if (a.epi == EPI_SWIGLU) klaunch(gemm_pp_split_kernel<EPI_SWIGLU>, dim3(nmain + ntail), dim3(512), s, hd, tl, nmain);
             else if (a.epi == EPI_HEADPOST) gemm_pp_split_kernel<EPI_HEADPOST><<<nmain + ntail, 512, 0, s>>>(hd, tl, nmain);
@@ -1343,6 +1560,11 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
     if (v == 7 || v == 8) {
         const int rc = gemm_tail_split(a, v, s);
         if (rc <= 0) return rc;   // split done (0) or failed (< 0); 1 = not applicable
+    }
+    // a multi-round SwiGLU grid of 256² tiles without a tail split: the same persistent walk
+    if (v == 7 && a.epi == EPI_SWIGLU && knobs().gemm_persist) {
+        const int64_t tiles = (int64_t)((a.M + 255) / 256) * (a.N / 256);
+        if (tiles > plan_cus() && tiles < (1ll << 30)) return launch_pp_persist(a, a, (int)tiles, 0, s);
     }
     return gemm_variant(a, v, s);
 }
