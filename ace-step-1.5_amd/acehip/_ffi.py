@@ -30,7 +30,8 @@ EXPORTS = [
     "acehip_vae_decode_blocks",
     "acehip_vae_encode", "acehip_vae_destroy", "acehip_vae_conv", "acehip_vae_resunit",
     "acehip_wav_peak_normalize", "acehip_wav_postprocess", "acehip_wav_postprocess_pcm16",
-    "acehip_gemm_bf16", "acehip_gemm_bf16_ex", "acehip_attention_bf16",
+    "acehip_gemm_bf16", "acehip_gemm_bf16_ex", "acehip_gemm_res_bf16", "acehip_gemm_res_norm_bf16",
+    "acehip_attention_bf16",
     "acehip_rmsnorm_bf16", "acehip_gemm_headpost_bf16", "acehip_attention_masked_bf16",
     "acehip_enc_create", "acehip_enc_set_weight", "acehip_enc_finalize", "acehip_enc_embed",
     "acehip_enc_forward", "acehip_enc_destroy", "acehip_fsq_quantize", "acehip_fsq_codes_from_indices",
@@ -112,6 +113,10 @@ def _declare(lib):
         "acehip_gemm_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P]),
         "acehip_gemm_bf16_ex": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, c_int,
                                         c_int, P]),
+        "acehip_gemm_res_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int64,
+                                         c_int, c_int, P]),
+        "acehip_gemm_res_norm_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int64, c_int, c_int,
+                                              P, P, P, c_int64, P, c_int, c_float, P, c_int, POINTER(c_int), P]),
         "acehip_attention_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_float, P]),
         "acehip_attention_masked_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -1037,6 +1037,64 @@ int acehip_gemm_bf16_ex(const void *A, int lda, const void *W, int ldw, void *C,
     return gemm_variant(g, variant, (hipStream_t)stream);
 }
 
+// residual-epilogue GemmArgs of the two test entry points below (gate == null: EPI_RES)
+static int res_gemm_args(GemmArgs &g, const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M,
+                         int N, int K, const void *res, int ldr, const void *gate, int64_t gate_bstride,
+                         int rows_per_batch) {
+    if (!A || !W || !C || !res) return fail(ACEHIP_E_ARG, "gemm_res: null argument");
+    if (M <= 0 || N % 128 || K % 64 || K <= 0) return fail(ACEHIP_E_ARG, "gemm_res: shape");
+    if ((lda | ldw | ldc | ldr) % 8 || lda < K || ldw < K || ldc < N || ldr < N)
+        return fail(ACEHIP_E_ARG, "gemm_res: leading dimensions");
+    if (gate && (rows_per_batch <= 0 || gate_bstride % 8)) return fail(ACEHIP_E_ARG, "gemm_res: gate");
+    g.A = (const bf16_t *)A; g.lda = lda; g.W = (const bf16_t *)W; g.ldw = ldw;
+    g.C = (bf16_t *)C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    g.res = (const bf16_t *)res; g.ldr = ldr;
+    g.epi = gate ? EPI_GATED_RES : EPI_RES;
+    g.gate = (const bf16_t *)gate; g.gate_bstride = gate_bstride; g.rows_per_batch = gate ? rows_per_batch : 0;
+    return 0;
+}
+
+int acehip_gemm_res_bf16(const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M, int N, int K,
+                         const void *res, int ldr, const void *gate, int64_t gate_bstride, int rows_per_batch,
+                         int variant, void *stream) {
+    GemmArgs g{};
+    if (int rc = res_gemm_args(g, A, lda, W, ldw, C, ldc, M, N, K, res, ldr, gate, gate_bstride, rows_per_batch))
+        return rc;
+    if (variant < 0) {   // production dispatch (split-K for small grids)
+        g.ws = abi_gemm_ws();
+        g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
+        return gemm(g, (hipStream_t)stream);
+    }
+    return gemm_variant(g, variant, (hipStream_t)stream);
+}
+
+int acehip_gemm_res_norm_bf16(const void *A, int lda, const void *W, int ldw, void *X, int M, int D, int K,
+                              const void *gate, int64_t gate_bstride, int rows_per_batch, int defer,
+                              const void *w, const void *shift, const void *scale, int64_t mod_bstride, void *out,
+                              int M_norm, float eps, const void *v, int from, int *deferred, void *stream) {
+    if (!w || !out || !deferred) return fail(ACEHIP_E_ARG, "gemm_res_norm: null argument");
+    if (M_norm < M || (v && (from < M || from > M_norm))) return fail(ACEHIP_E_ARG, "gemm_res_norm: rows");
+    // what rmsnorm_mod would refuse, before the GEMM has written X
+    if (D % 256 || D > 4096) return fail(ACEHIP_E_ARG, "gemm_res_norm: D must be a multiple of 256, <= 4096");
+    if ((shift == nullptr) != (scale == nullptr)) return fail(ACEHIP_E_ARG, "gemm_res_norm: shift/scale");
+    if ((gate || scale) && rows_per_batch <= 0) return fail(ACEHIP_E_ARG, "gemm_res_norm: rows_per_batch");
+    *deferred = 0;
+    GemmArgs g{};
+    if (int rc = res_gemm_args(g, A, lda, W, ldw, X, D, M, D, K, X, D, gate, gate_bstride, rows_per_batch)) return rc;
+    g.ws = abi_gemm_ws();
+    g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
+    RowAdd ra{};
+    if (int rc = gemm(g, (hipStream_t)stream, defer ? &ra : nullptr)) return rc;
+    *deferred = ra.part != nullptr;
+    if (v) {
+        ra.xw = (bf16_t *)X;
+        ra.v = (const bf16_t *)v;
+        ra.from = from;
+    }
+    return rmsnorm_mod((const bf16_t *)X, (const bf16_t *)w, (const bf16_t *)shift, (const bf16_t *)scale,
+                       mod_bstride, rows_per_batch, (bf16_t *)out, M_norm, D, eps, (hipStream_t)stream, ra);
+}
+
 int acehip_rmsnorm_bf16(const void *x, const void *w, const void *shift, const void *scale,
                         int64_t mod_bstride, int rows_per_batch, void *out, int M, int D, float eps,
                         int rows_per_wave, void *stream) {

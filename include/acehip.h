@@ -438,6 +438,31 @@ int acehip_gemm_bf16(const void *A, int lda, const void *W, int ldw, void *C, in
 int acehip_gemm_bf16_ex(const void *A, int lda, const void *W, int ldw, void *C, int ldc,
                         int M, int N, int K, const void *bias, int epi, int variant, void *stream);
 
+/* The residual epilogues, for tests: C = bf16(res + bf16(acc)) with gate == NULL, else the
+ * AdaLN-Zero gated form C = bf16(res + bf16(bf16(acc) · gate[m / rows_per_batch][n])), gate row b
+ * at gate + b·gate_bstride (ceil(M / rows_per_batch) rows of N).  res [M][ldr] may be C itself
+ * (in place) or a buffer of its own; rows >= M of C and columns >= N are not written.
+ * variant as in acehip_gemm_bf16_ex (-1: the production choice with the shared split-K
+ * workspace, whose epilogue then runs in the split-K reduction kernel). */
+int acehip_gemm_res_bf16(const void *A, int lda, const void *W, int ldw, void *C, int ldc,
+                         int M, int N, int K, const void *res, int ldr, const void *gate,
+                         int64_t gate_bstride, int rows_per_batch, int variant, void *stream);
+
+/* A residual GEMM and the norm that consumes it, as the DiT layer issues the pair (tests):
+ *   X[0:M] = residual epilogue (as above, in place, N = ldc = D) of A[M,K] · W[D,K]^T
+ *   X[from:M_norm] = bf16(X + v[D])                         (v != NULL; M <= from <= M_norm)
+ *   out[0:M_norm] = acehip_rmsnorm_bf16(X, w, shift, scale, mod_bstride, rows_per_batch)
+ * rows_per_batch is both the gate's and the modulation's batch size (> 0 when either is given), as
+ * in the DiT layer; D % 256 == 0, D <= 4096; arguments are checked before X is written.
+ * With defer != 0 a GEMM that takes the split-K path leaves its epilogue to the norm kernel,
+ * which then applies it from the fp32 partials in the same pass (ACEHIP_SPLITK_FUSE=0: never);
+ * *deferred (host int) reports whether it did.  X [M_norm][D] is updated in place either way. */
+int acehip_gemm_res_norm_bf16(const void *A, int lda, const void *W, int ldw, void *X, int M, int D, int K,
+                              const void *gate, int64_t gate_bstride, int rows_per_batch, int defer,
+                              const void *w, const void *shift, const void *scale, int64_t mod_bstride,
+                              void *out, int M_norm, float eps, const void *v, int from, int *deferred,
+                              void *stream);
+
 /* Flash attention, head_dim 128, GQA: q [B,H,Sq,128], k/v [B,KV,Sk,128] →
  * o [B,Sq,H*128]; window -1 = full, >= 0 |i-j| <= window, -2 = causal
  * (keys j <= i; the Qwen3 text encoder's default mask). */
