@@ -38,6 +38,7 @@ EXPORTS = [
     "acehip_attention_probs_bf16", "acehip_dit_forward_capture",
     "acehip_enc_kv_create", "acehip_enc_prefill", "acehip_enc_decode",
     "acehip_attention_decode_ws_bytes", "acehip_attention_decode_bf16", "acehip_lm_head_bf16",
+    "acehip_diag_pp_src_check",
 ]
 
 
@@ -115,6 +116,9 @@ def _declare(lib):
                                         c_int, P]),
         "acehip_gemm_res_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, c_int64,
                                          c_int, c_int, P]),
+        "acehip_diag_pp_src_check": (c_int64, [c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int,
+                                               POINTER(c_int), POINTER(c_int64), POINTER(c_int64),
+                                               POINTER(c_int64)]),
         "acehip_gemm_res_norm_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int64, c_int, c_int,
                                               P, P, P, c_int64, P, c_int, c_float, P, c_int, POINTER(c_int), P]),
         "acehip_attention_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -26,8 +26,11 @@
 //     overlap on every SIMD), picked per shape by gemm_pick_variant.
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 #include "headpost.h"
+#include "pp_addr.h"
 
 namespace acehip {
 namespace {
@@ -608,24 +611,18 @@ __device__ __forceinline__ void pp_tile_origin(const GemmArgs &a, int bid, int s
 }
 
 // Source addresses of a wave's LDS-DMA pieces, one 64-bit pointer per piece and lane (the tile
-// a one-tile workgroup keeps for its whole life)
+// a one-tile workgroup keeps for its whole life).  The integer arithmetic of both sets is
+// pp_addr.h's, which host code can call (acehip_diag_pp_src_check)
 template <int BM>
 struct PPSrcPtr {
     static constexpr int NA = BM / 64, NB = 4;               // glds per wave for A / B of one K-tile
+    static constexpr bool SCALAR = false;
     const bf16_t *pa[NA], *pb[NB];
     __device__ __forceinline__ void set(const GemmArgs &a, int m0, int n0, int wave, int lane) {
 #pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int r = (wave + 8 * i) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            pa[i] = a.A + (int64_t)min(m0 + r, a.M - 1) * a.lda + c * 8;
-        }
+        for (int i = 0; i < NA; ++i) pa[i] = a.A + pp_ptr_a(a.M, a.lda, m0, wave, lane, i);
 #pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            const int r = (wave + 8 * i) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ (((BM + r) >> 1) & 7);
-            pb[i] = a.W + (int64_t)(n0 + r) * a.ldw + c * 8;
-        }
+        for (int i = 0; i < NB; ++i) pb[i] = a.W + pp_ptr_b(BM, a.ldw, n0, wave, lane, i);
     }
     // piece i of the K-tile at element offset k0 → the wave's 1 KiB LDS slot
     __device__ __forceinline__ void dmaA(int i, int k0, char *dst) const { glds16(pa[i] + k0, dst); }
@@ -648,18 +645,17 @@ __device__ __forceinline__ void glds16_s(const char *sbase, uint32_t voff, char 
 template <int BM>
 struct PPSrcOff {
     static constexpr int NA = BM / 64, NB = 4;
+    static constexpr bool SCALAR = true;   // the LDS slot address is scalar too: `wave` must be wave-uniform
+    static_assert(BM % 16 == 0, "A and W image rows share the swizzle chunk");
     const char *ba, *bb;
     uint32_t oa[NA], ob, bstep;
     __device__ __forceinline__ void set(const GemmArgs &a, int m0, int n0, int wave, int lane) {
         ba = (const char *)(a.A + (int64_t)m0 * a.lda);
         bb = (const char *)(a.W + (int64_t)n0 * a.ldw);
-        bstep = 64u * (uint32_t)a.ldw * 2u;
-        const int r0 = wave * 8 + (lane >> 3);
-        const uint32_t c16 = (uint32_t)((lane & 7) ^ ((r0 >> 1) & 7)) * 16u;
-        ob = (uint32_t)r0 * (uint32_t)a.ldw * 2u + c16;
-        const int last = a.M - 1 - m0;
+        bstep = pp_off_bstep(a.ldw);
+        ob = pp_off_b(a.ldw, wave, lane);
 #pragma unroll
-        for (int i = 0; i < NA; ++i) oa[i] = (uint32_t)min(r0 + 64 * i, last) * (uint32_t)a.lda * 2u + c16;
+        for (int i = 0; i < NA; ++i) oa[i] = pp_off_a(a.M, a.lda, m0, wave, lane, i);
     }
     __device__ __forceinline__ void dmaA(int i, int k0, char *dst) const { glds16_s(ba + (int64_t)k0 * 2, oa[i], dst); }
     __device__ __forceinline__ void dmaB(int i, int k0, char *dst) const {
@@ -675,8 +671,7 @@ __device__ __forceinline__ void pp_stageA(const GemmArgs &a, char *lds, const Sr
     if constexpr (EPI == EPI_CONV) {
         // implicit-GEMM conv: K-tile k0 = tap·cin + c0 reads the input rows shifted by
         // conv_a0 + tap·dil (zero halo rows around the activation)
-        const int cin = a.conv_cin, tap = k0 / cin;
-        ko = k0 + tap * (a.conv_dil - 1) * cin + a.conv_a0 * cin;
+        ko = pp_conv_ko(k0, a.conv_cin, a.conv_dil, a.conv_a0);
     }
 #pragma unroll
     for (int i = 0; i < Src::NA; ++i) src.dmaA(i, ko, b + (wave + 8 * i) * 1024);
@@ -719,7 +714,7 @@ __device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src 
     static_assert(SM % 2 == 0, "A half must be whole 16-row sub-tiles");
     const int tid = threadIdx.x, lane = tid & 63;
     int wave = tid >> 6;
-    if constexpr (PERSIST) wave = __builtin_amdgcn_readfirstlane(wave);   // scalar LDS slot addresses (glds16_s)
+    if constexpr (Src::SCALAR) wave = __builtin_amdgcn_readfirstlane(wave);   // scalar LDS slot addresses (glds16_s)
     const int wr = wave >> 2, wc = wave & 3;
     auto stageA = [&](int buf, int k0) { pp_stageA<BM, EPI>(a, lds, src, wave, buf, k0); };
     auto stageB = [&](int buf, int k0) { pp_stageB<BM>(lds, src, wave, buf, k0); };
@@ -851,14 +846,21 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &a, char *lds, const 
     epilogue_tile<SM, 4, EPI>(a, acc, m0 + arow, n0 + wc * 64, fr, fc);
 }
 
-template <int BM, int EPI>
+// SADDR (ACEHIP_GEMM_SADDR, chosen at launch): the K loop issues its LDS-DMAs from the tile's
+// scalar base + 32-bit lane offsets (PPSrcOff) — per piece an s_add_u32 / s_addc_u32 / s_mov m0 —
+// instead of a 64-bit pointer per piece and lane (PPSrcPtr: per piece and K-tile a
+// v_lshl_add_u64, a v_readfirstlane → m0 chain and a v_add_u32, in the read phase that has to
+// fit under the other wave group's MFMA interval).  The same addresses (pp_addr.h), so the same
+// bits; the host takes this form only where the 32-bit offsets cannot wrap (pp_saddr_fits).
+template <int BM, int EPI, bool SADDR>
 __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int bid) {
     GSTAMP(0);
     GSTAMP_REAL(4);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = SADDR ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     int m0, n0;
     pp_tile_origin<BM>(a, bid, blockIdx.x, m0, n0);
-    PPSrcPtr<BM> src;
+    std::conditional_t<SADDR, PPSrcOff<BM>, PPSrcPtr<BM>> src;
     src.set(a, m0, n0, wave, lane);
     f32x4 acc[BM / 32][4];
     pp_main<BM, EPI, false>(a, lds, src, acc, blockIdx.x, -1);
@@ -947,21 +949,21 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, Gem
     }
 }
 
-template <int BM, int EPI>
+template <int BM, int EPI, bool SADDR>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<BM>()];
-    gemm_pp_body<BM, EPI>(a, lds, blockIdx.x);
+    gemm_pp_body<BM, EPI, SADDR>(a, lds, blockIdx.x);
 }
 
 // The tail-split GEMM (gemm_tail_split: whole rounds of 256-row tiles + the remaining rows as
 // one round of 128-row tiles) in ONE launch: blocks [0, nmain) run the main grid, the rest the
 // tail grid, so the tail's blocks start on CUs as the main grid's last round drains instead of
 // behind a kernel boundary
-template <int EPI>
+template <int EPI, bool SADDR>
 __global__ __launch_bounds__(512, 1) void gemm_pp_split_kernel(GemmArgs a, GemmArgs t, int nmain) {
     __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<256>()];
-    if ((int)blockIdx.x < nmain) gemm_pp_body<256, EPI>(a, lds, blockIdx.x);
-    else gemm_pp_body<128, EPI>(t, lds, blockIdx.x - nmain);
+    if ((int)blockIdx.x < nmain) gemm_pp_body<256, EPI, SADDR>(a, lds, blockIdx.x);
+    else gemm_pp_body<128, EPI, SADDR>(t, lds, blockIdx.x - nmain);
 }
 
 // ---------------------------------------------------------------------------
@@ -1184,24 +1186,33 @@ int launch_w4(const GemmArgs &a, hipStream_t s) {
     return 0;
 }
 
-template <int BM>
-int launch_pp(const GemmArgs &a, hipStream_t s) {
+// Whether a one-tile ping-pong launch of BM-row tiles takes the scalar-base K loop
+// (gemm_pp_body SADDR): ACEHIP_GEMM_SADDR, and leading dimensions whose 32-bit lane offsets
+// cannot wrap — anything else keeps the pointer form, so no call that works there fails here.
+// The store / residual / SwiGLU epilogues and the fused main + tail launch (head-post included)
+// take it; the conv epilogue and the one-launch head-post grid (layer 0's deduplicated QKV) stay
+// on the pointer form — in the round-8 A/B they were ahead with it, but not by twice the
+// same-vs-same spread in every round, so they have no scalar-base instantiation.
+static bool pp_use_saddr(const GemmArgs &a, int BM) { return knobs().gemm_saddr && pp_saddr_fits(BM, a.lda, a.ldw); }
+
+template <int BM, bool SADDR>
+int launch_pp_as(const GemmArgs &a, hipStream_t s) {
     if (a.N % 256) return fail(-1, "gemm: N not a multiple of 256");
     const int tiles = ((a.M + BM - 1) / BM) * (a.N / 256);
     switch (a.epi) {
-        case EPI_STORE: gemm_pp_kernel<BM, EPI_STORE><<<tiles, 512, 0, s>>>(a); break;
-        case EPI_GATED_RES: gemm_pp_kernel<BM, EPI_GATED_RES><<<tiles, 512, 0, s>>>(a); break;
-        case EPI_RES: gemm_pp_kernel<BM, EPI_RES><<<tiles, 512, 0, s>>>(a); break;
-        case EPI_SWIGLU: klaunch(gemm_pp_kernel<BM, EPI_SWIGLU>, dim3(tiles), dim3(512), s, a); break;
+        case EPI_STORE: gemm_pp_kernel<BM, EPI_STORE, SADDR><<<tiles, 512, 0, s>>>(a); break;
+        case EPI_GATED_RES: gemm_pp_kernel<BM, EPI_GATED_RES, SADDR><<<tiles, 512, 0, s>>>(a); break;
+        case EPI_RES: gemm_pp_kernel<BM, EPI_RES, SADDR><<<tiles, 512, 0, s>>>(a); break;
+        case EPI_SWIGLU: klaunch(gemm_pp_kernel<BM, EPI_SWIGLU, SADDR>, dim3(tiles), dim3(512), s, a); break;
         case EPI_CONV:
             if constexpr (BM == 256 || BM == 128) {
-                gemm_pp_kernel<BM, EPI_CONV><<<tiles, 512, 0, s>>>(a);
+                gemm_pp_kernel<BM, EPI_CONV, false><<<tiles, 512, 0, s>>>(a);
                 break;
             }
             return fail(-1, "gemm: the conv epilogue runs on the 256- or 128-row ping-pong tile");
         case EPI_HEADPOST:
             if constexpr (BM == 256 || BM == 192 || BM == 128) {
-                gemm_pp_kernel<BM, EPI_HEADPOST><<<tiles, 512, 0, s>>>(a);
+                gemm_pp_kernel<BM, EPI_HEADPOST, false><<<tiles, 512, 0, s>>>(a);
                 break;
             }
             return fail(-1, "gemm: head-post epilogue needs the 256-, 192- or 128-row ping-pong tile");
@@ -1209,6 +1220,10 @@ int launch_pp(const GemmArgs &a, hipStream_t s) {
     }
     HIP_TRY(hipGetLastError());
     return 0;
+}
+template <int BM>
+int launch_pp(const GemmArgs &a, hipStream_t s) {
+    return pp_use_saddr(a, BM) ? launch_pp_as<BM, true>(a, s) : launch_pp_as<BM, false>(a, s);
 }
 
 template <int BM, int BN, int WM, int WN, int STAGES, int NH = 0>
@@ -1444,12 +1459,20 @@ static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
         // blocks' XCD is their own index mod 8, as in a launch of their own)
         const int nmain = (int)(full * cus / nN * nN), ntail = ((tl.M + 127) / 128) * (int)nN;
         // SwiGLU: one persistent walk over both grids (ACEHIP_GEMM_PERSIST=0: the launch below)
-        if (a.epi == EPI_SWIGLU && knobs().gemm_persist && nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0)
+        if (a.epi == EPI_SWIGLU && knobs().gemm_persist && pp_saddr_fits(256, a.lda, a.ldw) &&
+            nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0)
             return launch_pp_persist(hd, tl, nmain, ntail, s);
         if (nmain % 8 == 0 && nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0) {
-            if (a.epi == EPI_SWIGLU) klaunch(gemm_pp_split_kernel<EPI_SWIGLU>, dim3(nmain + ntail), dim3(512), s, hd, tl, nmain);
-            else if (a.epi == EPI_HEADPOST) gemm_pp_split_kernel<EPI_HEADPOST><<<nmain + ntail, 512, 0, s>>>(hd, tl, nmain);
-            else gemm_pp_split_kernel<EPI_STORE><<<nmain + ntail, 512, 0, s>>>(hd, tl, nmain);
+            const dim3 grid(nmain + ntail), block(512);
+            if (pp_use_saddr(a, 256)) {   // head and tail share lda / ldw; 256 rows bound both tiles
+                if (a.epi == EPI_SWIGLU) klaunch(gemm_pp_split_kernel<EPI_SWIGLU, true>, grid, block, s, hd, tl, nmain);
+                else if (a.epi == EPI_HEADPOST) gemm_pp_split_kernel<EPI_HEADPOST, true><<<grid, block, 0, s>>>(hd, tl, nmain);
+                else gemm_pp_split_kernel<EPI_STORE, true><<<grid, block, 0, s>>>(hd, tl, nmain);
+            } else {
+                if (a.epi == EPI_SWIGLU) klaunch(gemm_pp_split_kernel<EPI_SWIGLU, false>, grid, block, s, hd, tl, nmain);
+                else if (a.epi == EPI_HEADPOST) gemm_pp_split_kernel<EPI_HEADPOST, false><<<grid, block, 0, s>>>(hd, tl, nmain);
+                else gemm_pp_split_kernel<EPI_STORE, false><<<grid, block, 0, s>>>(hd, tl, nmain);
+            }
             HIP_TRY(hipGetLastError());
             return 0;
         }
@@ -1462,7 +1485,7 @@ static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
 // the conv epilogue on 64-row ping-pong tiles
 static int launch_conv64(const GemmArgs &a, hipStream_t s) {
     const int tiles = ((a.M + 63) / 64) * (a.N / 256);
-    gemm_pp_kernel<64, EPI_CONV><<<tiles, 512, 0, s>>>(a);
+    gemm_pp_kernel<64, EPI_CONV, false><<<tiles, 512, 0, s>>>(a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1562,7 +1585,7 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
         if (rc <= 0) return rc;   // split done (0) or failed (< 0); 1 = not applicable
     }
     // a multi-round SwiGLU grid of 256² tiles without a tail split: the same persistent walk
-    if (v == 7 && a.epi == EPI_SWIGLU && knobs().gemm_persist) {
+    if (v == 7 && a.epi == EPI_SWIGLU && knobs().gemm_persist && pp_saddr_fits(256, a.lda, a.ldw)) {
         const int64_t tiles = (int64_t)((a.M + 255) / 256) * (a.N / 256);
         if (tiles > plan_cus() && tiles < (1ll << 30)) return launch_pp_persist(a, a, (int)tiles, 0, s);
     }
@@ -1570,3 +1593,56 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
 }
 
 }  // namespace acehip
+
+// Host-only check of the two source-address forms (tests; no GPU call): for every row tile, column
+// tile, wave, lane, piece and K-tile of a BM × 256 ping-pong grid, the byte address relative to A / W
+// formed as the pointer form does (64-bit per lane) and as the scalar-base form does (64-bit tile
+// base + K offset, plus the lane's offset in 32-bit wrap-around arithmetic, zero-extended — what
+// global_load_lds with an SGPR base adds).  An A address depends on the row tile only and a W
+// address on the column tile only, so the two are walked separately.
+extern "C" int64_t acehip_diag_pp_src_check(int M, int N, int K, int64_t lda, int64_t ldw, int BM, int conv_cin,
+                                            int conv_dil, int conv_a0, int *fits, int64_t *min_a, int64_t *max_a,
+                                            int64_t *max_b) {
+    using namespace acehip;
+    if (M <= 0 || N <= 0 || N % 256 || K <= 0 || K % BK || lda <= 0 || ldw <= 0 ||
+        (BM != 64 && BM != 128 && BM != 192 && BM != 256) ||
+        (conv_cin && (conv_cin < 0 || conv_cin % BK || K % conv_cin || conv_dil < 1))) {
+        fail(-1, "diag_pp_src_check: M, N % 256, K % 64, BM in {64, 128, 192, 256}, conv_cin % 64");
+        return -1;
+    }
+    int64_t bad = 0, lo = INT64_MAX, hi_a = INT64_MIN, hi_b = INT64_MIN;
+    const int nk = K / BK, NA = BM / 64;
+    for (int m0 = 0; m0 < M; m0 += BM)
+        for (int wave = 0; wave < 8; ++wave)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < NA; ++i) {
+                    const int64_t p = pp_ptr_a(M, lda, m0, wave, lane, i) * 2, base = (int64_t)m0 * lda * 2;
+                    const uint32_t off = pp_off_a(M, lda, m0, wave, lane, i);
+                    for (int kt = 0; kt < nk; ++kt) {
+                        const int ko = conv_cin ? pp_conv_ko(kt * BK, conv_cin, conv_dil, conv_a0) : kt * BK;
+                        const int64_t ap = p + (int64_t)ko * 2, as = base + (int64_t)ko * 2 + (int64_t)(uint64_t)off;
+                        bad += ap != as;
+                        lo = std::min(lo, ap);
+                        hi_a = std::max(hi_a, ap + 15);
+                    }
+                }
+    const uint32_t bstep = pp_off_bstep(ldw);
+    for (int n0 = 0; n0 < N; n0 += 256)
+        for (int wave = 0; wave < 8; ++wave)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < 4; ++i) {
+                    const int64_t p = pp_ptr_b(BM, ldw, n0, wave, lane, i) * 2;
+                    const int64_t base = (int64_t)n0 * ldw * 2 + (int64_t)((uint64_t)i * bstep);
+                    const uint32_t off = pp_off_b(ldw, wave, lane);
+                    for (int kt = 0; kt < nk; ++kt) {
+                        const int64_t bp = p + (int64_t)kt * BK * 2, bs = base + (int64_t)kt * BK * 2 + (int64_t)(uint64_t)off;
+                        bad += bp != bs;
+                        hi_b = std::max(hi_b, bp + 15);
+                    }
+                }
+    if (fits) *fits = pp_saddr_fits(BM, lda, ldw) ? 1 : 0;
+    if (min_a) *min_a = lo;
+    if (max_a) *max_a = hi_a;
+    if (max_b) *max_b = hi_b;
+    return bad;
+}

@@ -37,6 +37,7 @@ Knobs read_env() {
     k.convt = env_int("ACEHIP_CONVT", 1);
     k.gemm_hp_tail = env_int("ACEHIP_GEMM_HPTAIL", 1);
     k.gemm_persist = env_int("ACEHIP_GEMM_PERSIST", 1);
+    k.gemm_saddr = env_int("ACEHIP_GEMM_SADDR", 1);
     k.gemm_cus = env_int("ACEHIP_GEMM_CUS", 0);
     k.convp = env_int("ACEHIP_CONVP", 3);
     k.ru7 = env_int("ACEHIP_RU7", 2);

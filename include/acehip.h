@@ -448,6 +448,20 @@ int acehip_gemm_res_bf16(const void *A, int lda, const void *W, int ldw, void *C
                          int M, int N, int K, const void *res, int ldr, const void *gate,
                          int64_t gate_bstride, int rows_per_batch, int variant, void *stream);
 
+/* Host-only check, for tests (no GPU call): the ping-pong GEMM tiles (BM x 256, BM in {64, 128,
+ * 192, 256}; variants 7-9 and the implicit-GEMM convs) fetch their operands by LDS-DMA from
+ * addresses formed either as a 64-bit pointer per lane or as a scalar tile base plus a 32-bit
+ * lane offset (ACEHIP_GEMM_SADDR).  For every row / column tile, wave, lane, piece and K-tile of
+ * an [M, K] x [N, K]^T grid this forms both and returns the number of pieces whose byte address
+ * differs (-1: bad arguments).  conv_cin != 0: the A-side K offset of an implicit-GEMM conv
+ * (conv_cin channels per tap, dilation conv_dil, first tap at input row m + conv_a0).
+ * *fits: whether the library would take the scalar form for these leading dimensions;
+ * *min_a / *max_a, *max_b: the lowest / highest byte offset from A, and the highest from W,
+ * that any piece touches (its last byte).  Any out pointer may be NULL. */
+int64_t acehip_diag_pp_src_check(int M, int N, int K, int64_t lda, int64_t ldw, int BM, int conv_cin,
+                                 int conv_dil, int conv_a0, int *fits, int64_t *min_a, int64_t *max_a,
+                                 int64_t *max_b);
+
 /* A residual GEMM and the norm that consumes it, as the DiT layer issues the pair (tests):
  *   X[0:M] = residual epilogue (as above, in place, N = ldc = D) of A[M,K] · W[D,K]^T
  *   X[from:M_norm] = bf16(X + v[D])                         (v != NULL; M <= from <= M_norm)

@@ -62,6 +62,8 @@ for _ in range(int(os.environ.get("ROUNDS", "3"))):
         for k in st:
             os.environ.pop(k)
             reload_knobs()
+for r in range(len(times[0])):   # every round, so a repeated setting gives the same-vs-same spread
+    print(f"round {r}: " + "  ".join(f"{t[r]:.1f}" for t in times) + " ms", flush=True)
 for i, st in enumerate(settings):
     same = torch.equal(outs[i], outs[0])
     print(f"{','.join(f'{a}={b}' for a, b in st.items()) or 'default'}: DiT song {statistics.median(times[i]):.1f} ms "
