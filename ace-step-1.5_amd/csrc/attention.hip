@@ -86,14 +86,14 @@ struct SplitArgs {
 // ds_read_b64_tr_b16 by inline asm (see pv() for why not the builtin)
 __device__ __forceinline__ s16x4 ds_read_tr16(const char *lds_ptr) {
     s16x4 r;
-    const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds_ptr;
+    const uint32_t a = lds_addr(lds_ptr);
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(a));
     return r;
 }
 
 __device__ __forceinline__ bf16x8 ds_read_b128(const char *lds_ptr) {
     bf16x8 r;
-    const uint32_t a = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds_ptr;
+    const uint32_t a = lds_addr(lds_ptr);
     asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(a));
     return r;
 }
@@ -116,8 +116,6 @@ __device__ __forceinline__ s16x4 ds_read_tr16_imm(uint32_t lane_off) {
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lane_off), "n"(OFF));
     return r;
 }
-template <int V>
-using IC = std::integral_constant<int, V>;
 // s_waitcnt lgkmcnt(0) that the listed fragments depend on (nothing using them can be
 // scheduled above it)
 __device__ __forceinline__ void lgkm_wait8(bf16x8 (&f)[8]) {
@@ -304,7 +302,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // expcnt(7) lgkmcnt(15)); otherwise its waitcnt pass, which cannot tell the loop's
     // LDS-DMAs from these register loads, re-waits vmcnt(0) at the first use of qf in
     // every tile — draining the K/V ring (cdna_hip_programming.md §5 trap (b))
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __builtin_amdgcn_s_waitcnt(waitcnt_enc(0, 15));
 
     const bf16_t *kp = k + ((int64_t)b * KV + kvh) * (int64_t)Sk * 128;
     const bf16_t *vp = v + ((int64_t)b * KV + kvh) * (int64_t)Sk * 128;
@@ -358,7 +356,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // LDS byte address of the ring (uniform) and the per-lane swizzled offsets:
     // K fragment (row r [+32], logical chunk 2s+hh) — the swizzle depends on row & 15 only;
     // Vᵀ fragment (d-block dt, row 4(g>>1)+qq [+8]) — rows +16s, +32t are uniform offsets
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds;
+    const uint32_t lds_base = lds_addr(lds);
     uint32_t koff[8], voff[4][2];
 #pragma unroll
     for (int s = 0; s < 8; ++s) koff[s] = lds_base + kvoff(r, 2 * s + hh);
@@ -424,7 +422,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // for the refill of its slot) — a raw s_barrier: __syncthreads() would add a full
     // vmcnt(0) drain
     auto tile_barrier = [&] {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
@@ -548,7 +546,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         const int64_t wsz = 66 * 64;                   // floats per wave: 64 O + m + l per lane
         float *const ws_u = sp.ws + (int64_t)(u - sp.full) * nsplit * 8 * wsz;
         slab_store(ws_u + ((int64_t)part * 8 + wave) * wsz, oacc, m, l, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         __shared__ int s_ticket;
         if (tid == 0) s_ticket = atomicAdd(sp.cnt + (u - sp.full), 1);
@@ -592,7 +590,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         __shared__ int s_fold;
         if (pt0 > 0) {
             slab_store(slot(cw), oacc, m, l, lane);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             if (tid == 0) s_fold = atomicAdd(sp.cnt + c0, 1) == BIG + n;
             __syncthreads();
@@ -601,7 +599,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
             __syncthreads();
             if (!s_fold) {
                 slab_store(slot(cw), oacc, m, l, lane);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                wait_vm<0>();
                 __syncthreads();
                 if (tid == 0) s_fold = atomicAdd(sp.cnt + c0, 1) == BIG + n;
                 __syncthreads();
@@ -670,14 +668,6 @@ constexpr int PW_O = 0, PW_Q = 128, PW_K = 192;
 //   * PW_PV_NOP — tried: s_nop 1 before every P·V MFMA in place of one pf_fence per sub-block;
 //     the fence was kept, the other arm removed.
 
-// compile-time loop: f(IC<I>{}) for I in [I0, I1)
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void sfor(F &&f) {
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        sfor<I0 + 1, I1>(f);
-    }
-}
 // opaque redefinition: nothing reading x is scheduled above this point
 template <typename T>
 __device__ __forceinline__ void pin(T &x) { asm volatile("" : "+v"(x)); }
@@ -756,17 +746,6 @@ __device__ __forceinline__ void pw_kread(uint32_t lane_off) {
 }
 // XDL (8 passes) → VALU read of its result: 12 wait states
 __device__ __forceinline__ void xdl_pad(f32x16 &a, f32x16 &b) { asm volatile("s_nop 7\n\ts_nop 4" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ const void *pw_uniform(const void *p) {   // pointer known wave-uniform → SGPRs
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (const void *)(((uint64_t)hi << 32) | lo);
-}
-// LDS-DMA of one 1 KiB piece, saddr form (SGPR base, per-lane 32-bit offset); M0 (the LDS
-// destination) is written in the same statement
-__device__ __forceinline__ void pw_dma(const char *base, uint32_t voff, uint32_t lds_addr) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff),
-                 "s"(base) : "memory");
-}
 template <int A>
 __device__ __forceinline__ void pw_qload(const bf16_t *p) {
     asm volatile("global_load_dwordx4 a[%c0:%c1], %2, off" :: "n"(A), "n"(A + 3), "v"(p) : "memory");
@@ -859,7 +838,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
     // this wave's LDS-DMA source (waves 0-1 stage K, 2-3 V) of unit g's KV head, as SGPRs
     auto kv_base = [&](const UnitG &g) __attribute__((always_inline)) {
         const bf16_t *base = (wave < 2 ? k : v) + ((int64_t)g.b * KV + g.kvh) * (int64_t)Sk * 128;
-        return (const char *)pw_uniform(base);
+        return (const char *)uniform_ptr(base);
     };
     // Q of unit g → AGPRs a[128:191]
     auto load_q = [&](const UnitG &g) __attribute__((always_inline)) {
@@ -889,7 +868,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
     });
     asm volatile("s_nop 0" ::: "a0", "a255");
     load_q(geom(u, 0, 1));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     // 32 KiB tile = 32 LDS-DMA wave-instructions, 8 per wave
     // Whole tiles (kv0 + 64 ≤ Sk) go by the saddr form: SGPR base = K or V + the piece's first
     // key row (uniform: waves 0-1 stage K, 2-3 V), VGPR = the lane's swizzled 16-B slot, one of
@@ -902,15 +881,15 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
         dma_off[j] = (uint32_t)((lane >> 4) * 256 + (((lane & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4));
     }
     const char *kv_src = kv_base(geom(u, 0, 1));
-    const uint32_t lds_u = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds;
+    const uint32_t lds_u = lds_addr(lds);
     // tile at key kv0 of the KV head whose K (waves 0-1) or V (waves 2-3) base is src → ring slot buf
     auto stage_tile = [&](const char *src, int kv0, int buf) __attribute__((always_inline)) {
         if (kv0 + KT <= Sk) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int c = wave * 8 + i;
-                pw_dma(src + (int64_t)(kv0 + (c & 15) * 4) * 256, dma_off[i & 3],
-                       lds_u + ((c >> 4) * NBUF + buf) * TILE + (c & 15) * 1024);
+                glds16_s(src + (int64_t)(kv0 + (c & 15) * 4) * 256, dma_off[i & 3],
+                         lds_u + ((c >> 4) * NBUF + buf) * TILE + (c & 15) * 1024);
             }
             return;
         }
@@ -929,7 +908,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
     const char *nx_src = kv_src;
 
     const int g = lane >> 4, gi = lane & 15, qq = gi >> 2, pp = gi & 3;
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds;
+    const uint32_t lds_base = lds_addr(lds);
     uint32_t koff[8], voff[4][2];
 #pragma unroll
     for (int s = 0; s < 8; ++s) koff[s] = lds_base + kvoff(r, 2 * s + hh);
@@ -947,7 +926,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
         pw_kread<PW_K + 4 * i, KB + (i >> 3) * 32 * 256>(koff[i & 7]);
     };
     auto tile_barrier = [&] __attribute__((always_inline)) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
@@ -1061,7 +1040,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
                     for (int j = 0; j < 8; ++j) pf[sb][t][s][j] = (__bf16)st[sb][t][8 * s + j];
             if (__any(alpha[sb] != 1.0f)) pw_oscale<PW_O + 64 * sb>(alpha[sb]);
         };
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // K(it) in a[192:255]
+        wait_lgkm0();   // K(it) in a[192:255]
         if (!outside) {
             mx[0] = mx[1] = mx2[0] = mx2[1] = NEG;
             sfor<0, 16>([&](auto G) __attribute__((always_inline)) {     // phase 1
@@ -1177,7 +1156,7 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
             st_c(mine + 64 * 64 + lane, m[sb]);
             st_c(mine + 65 * 64 + lane, l[sb]);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         __shared__ int s_ticket;
         if (tid == 0) s_ticket = atomicAdd(sp.cnt + (u - sp.full), 1);
@@ -1214,8 +1193,8 @@ __global__ __launch_bounds__(256, 1) void attn_pw_kernel(const bf16_t *__restric
     if (has_next) {
         // the next unit's Q (16 loads) landed; only its tile-1 LDS-DMA (8 pieces, issued after
         // the Q loads) may still be in flight — before any store joins the vmcnt queue
-        if (n_nt >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (n_nt >= 2) wait_vm<8>();
+        else wait_vm<0>();
     }
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb) {
@@ -1356,7 +1335,7 @@ __global__ __launch_bounds__(256, 1) void attn_small_kernel(const bf16_t *__rest
         }
     };
     const int g = lane >> 4, gi = lane & 15, qq = gi >> 2, pp = gi & 3;
-    const uint32_t vbase = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)vl;
+    const uint32_t vbase = lds_addr(vl);
     uint32_t voff[4][2];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -1376,7 +1355,7 @@ __global__ __launch_bounds__(256, 1) void attn_small_kernel(const bf16_t *__rest
         const int kv0 = (t0 + wave + 4 * j) * KT;
         // this tile's K registers and V slot landed (issued one tile ago); the next tile's are
         // issued now, into the other slot, whose last reads retired inside the previous tile
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         if (j + 1 < nmine) {
             load_k(kv0 + 4 * KT, kn);
             stage_v(kv0 + 4 * KT, decltype(SLOTC)::value ^ 1);
@@ -1527,7 +1506,7 @@ __global__ __launch_bounds__(256, 1) void attn_small_kernel(const bf16_t *__rest
         // 8-wave slabs
         float *const wsu = ws + (int64_t)unit * nparts * (4 * 18 * 64);
         small_part_store(wsu + ((int64_t)part * 4 + wave) * 18 * 64, acc, mt, lt, lane);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         __shared__ int s_ticket;
         if (tid == 0) s_ticket = atomicAdd(cnt + unit, 1);
@@ -1577,15 +1556,7 @@ __global__ __launch_bounds__(256, 1) void attn_small_kernel(const bf16_t *__rest
 static int num_cus_attn() {
     // ACEHIP_ATTN_CUS overrides the CU count the tail split plans for (tests use it
     // to exercise 3- and 4-way splits on small shapes)
-    if (knobs().attn_cus > 0) return knobs().attn_cus;
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
+    return knobs().attn_cus > 0 ? knobs().attn_cus : device_cus();
 }
 
 // short-sequence KV split (a grid of a few units, e.g. the 10 s song's cross-attention: 8

@@ -190,15 +190,7 @@ __global__ __launch_bounds__(128) void attn_decode_fold_kernel(const float *__re
 }
 
 int decode_cus() {
-    if (knobs().attn_cus > 0) return knobs().attn_cus;
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
+    return knobs().attn_cus > 0 ? knobs().attn_cus : device_cus();
 }
 
 // ------------------------------------------------------------------ lm_head ---

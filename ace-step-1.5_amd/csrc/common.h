@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 typedef uint16_t bf16_t;  // raw bf16 bits in memory
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -183,6 +184,71 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 __device__ __forceinline__ void glds16(const void *gsrc, void *lds_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
                                      (__attribute__((address_space(3))) void *)lds_base, 16, 0, 0);
+}
+
+// 32-bit LDS address of a shared-memory pointer (what M0 and the ds instructions take)
+__device__ __forceinline__ uint32_t lds_addr(const void *p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)p;
+}
+// pointer known wave-uniform → SGPRs
+__device__ __forceinline__ const void *uniform_ptr(const void *p) {
+    const uint64_t v = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return (const void *)(((uint64_t)hi << 32) | lo);
+}
+// The same 1 KiB piece by inline asm with explicit counted waits (wait_vm below), in the saddr
+// form (glds16_s: SGPR base, which the caller must hold wave-uniform, + one 32-bit VGPR lane
+// offset) or with a 64-bit per-lane address (glds16_v):
+//  * the builtin LDS-DMA forms either build a 64-bit VGPR address per piece (hoisted out of an
+//    unrolled loop and spilled, and every spill reload waits vmcnt(0)) or, for the buffer form,
+//    make the compiler wait vmcnt(0) before every LDS read;
+//  * the compiler, not seeing these loads, inserts no vmcnt waits for them (loads that fill
+//    registers stay compiler-visible).
+// M0 (the LDS destination, lds_addr of it) is set in the same asm; nothing else in a kernel
+// that uses these may use M0.
+__device__ __forceinline__ void glds16_s(const void *sbase, uint32_t voff, uint32_t lds_dst) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase)
+                 : "memory");
+}
+__device__ __forceinline__ void glds16_v(const void *src, uint32_t lds_dst) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_dst), "v"(src)
+                 : "memory");
+}
+
+// ------------------------------------------------------------- s_waitcnt ---
+// Waits the compiler does not see (asm, for the asm DMAs above and as fences): own vector
+// memory operations retired down to N outstanding, and / or own LDS and scalar accesses retired.
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+    static_assert(0 <= N && N < 64, "vmcnt field");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vm_lgkm0() {
+    static_assert(0 <= N && N < 64, "vmcnt field");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// Operand of __builtin_amdgcn_s_waitcnt (the compiler-visible wait: its own waitcnt pass then
+// knows what has retired): vmcnt(vm) expcnt(7) lgkmcnt(lgkm); vmcnt is split over bits [3:0] and
+// [15:14], lgkmcnt sits in [11:8].  vm = 63 / lgkm = 15 leave that counter unwaited.
+constexpr int waitcnt_enc(int vm, int lgkm) { return (vm & 15) | ((vm >> 4) << 14) | 0x0070 | (lgkm << 8); }
+static_assert(waitcnt_enc(0, 0) == 0x0070 && waitcnt_enc(8, 0) == 0x0078, "s_waitcnt encoding");
+static_assert(waitcnt_enc(63, 0) == 0xC07F && waitcnt_enc(0, 15) == 0x0F70, "s_waitcnt encoding");
+
+// ------------------------------------------------------------ tile helpers --
+// byte offset of 16-B chunk `chunk` of row `row` in a 128-B-row LDS image, XOR-swizzled for
+// conflict-free ds_read_b128
+__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+// compile-time loop: f(IC<I>{}) for I in [I0, I1)
+template <int V>
+using IC = std::integral_constant<int, V>;
+template <int I0, int I1, typename F>
+__device__ __forceinline__ void sfor(F &&f) {
+    if constexpr (I0 < I1) {
+        f(IC<I0>{});
+        sfor<I0 + 1, I1>(f);
+    }
 }
 
 // bijective XCD-aware block remap (cdna_hip_programming.md §5 template)

@@ -31,8 +31,6 @@ namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
 // A-row source for im2col staging: row m, tap → in[m·a_stride + tap·dil + a_off][ci0 + 8c]
 // (a zero page outside [0, L_in) — glds cannot write zeros, it copies them)
 __device__ __forceinline__ const bf16_t *a_src(const ConvArgs &a, int64_t m, int tap, int ci0, int c) {
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvArgs a) {
     stage(0, 0);
     const int fr = lane & 15, fc = lane >> 4;
     for (int kt = 0; kt < nk; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BK);
@@ -185,25 +183,6 @@ constexpr int MAXN = 1024;                                // parameter image: N 
 constexpr int PAR = MAXN * 10;                            // bias bf16 | sa f32 | sib f32
 }  // namespace cp
 
-__device__ __forceinline__ void cp_dma_v(const void *src, uint32_t lds_addr) {   // 64-bit per-lane address
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src)
-                 : "memory");
-}
-__device__ __forceinline__ const void *cp_uniform(const void *p) {   // pointer known wave-uniform → SGPRs
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (const void *)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ void cp_dma_s(const void *base, uint32_t voff, uint32_t lds_addr) {   // saddr form
-    base = cp_uniform(base);
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base)
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cp_wait() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
 template <bool RES, bool RAW, bool SN>
 __global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitems, int phases) {
     constexpr int CBM = cp::BM, CBN = cp::BN, STG = cp::STAGE, PW = cp::PW, RW = RES ? cp::RW : 0;
@@ -228,8 +207,8 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitem
         pbias[c] = a.bias ? a.bias[c] : (bf16_t)0;
         if constexpr (SN) { psa[c] = a.sa[c]; psib[c] = a.sib[c]; }
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    const uint32_t l0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)lds;
+    __builtin_amdgcn_s_waitcnt(waitcnt_enc(0, 0));
+    const uint32_t l0 = lds_addr(lds);
     const uint32_t lst = l0 + cp::PAR, lres = lst + NS * STG;
     const char *stb = lds + cp::PAR, *resb = stb + NS * STG;
 
@@ -252,14 +231,14 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitem
         for (int i = 0; i < PW / 2; ++i) {                  // A: im2col rows (zero page outside)
             const int q = wave + cp::NW * i, r = q * 8 + r8;
             const int c = (lane & 7) ^ ((r >> 1) & 7);
-            cp_dma_v(a_src(a, s_m0 + r, tap, ci0, c), dst + q * 1024);
+            glds16_v(a_src(a, s_m0 + r, tap, ci0, c), dst + q * 1024);
         }
         const char *wb = (const char *)(a.W + (int64_t)s_phase * a.w_pstride + (int64_t)s_n0 * K + k0);
 #pragma unroll
         for (int i = PW / 2; i < PW; ++i) {                 // W rows
             const int q = wave + cp::NW * i, r = q * 8 + r8 - CBM;
             const int c = (lane & 7) ^ (((r + CBM) >> 1) & 7);
-            cp_dma_s(wb, (uint32_t)(r * K + c * 8) * 2, dst + q * 1024);
+            glds16_s(uniform_ptr(wb), (uint32_t)(r * K + c * 8) * 2, dst + q * 1024);
         }
         if (++s_slot == NS) s_slot = 0;
         if (++s_kt == nk) {
@@ -279,7 +258,7 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitem
             const int c = (lane & 15) ^ (r & 15);
             const int64_t m = min(m0 + r, a.M - 1);
             const int64_t row = min(max(m * a.c_stride + a.c_off + phase, (int64_t)0), a.L_out - 1);
-            cp_dma_v(a.res + row * a.N + n0 + c * 8, lres + q * 1024);
+            glds16_v(a.res + row * a.N + n0 + c * 8, lres + q * 1024);
         }
     };
 
@@ -312,9 +291,9 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitem
         const int extra = (rs ? RW : 0) + (st ? KST : 0);
 #define CP_W(E)                                                    \
     do {                                                           \
-        if (newer == 2) cp_wait<2 * PW + (E)>();                   \
-        else if (newer == 1) cp_wait<PW + (E)>();                  \
-        else cp_wait<(E)>();                                       \
+        if (newer == 2) wait_vm_lgkm0<2 * PW + (E)>();             \
+        else if (newer == 1) wait_vm_lgkm0<PW + (E)>();            \
+        else wait_vm_lgkm0<(E)>();                                 \
     } while (0)
         if (extra == RW + KST) CP_W(RW + KST);
         else if (extra == KST) CP_W(KST);
@@ -345,9 +324,9 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitem
         // stage g, all after it), then visible to every wave
         if (RES) {
             const int en = left < NS - 1 ? (int)left : NS - 1;
-            if (en == 2) cp_wait<2 * PW>();
-            else if (en == 1) cp_wait<PW>();
-            else cp_wait<0>();
+            if (en == 2) wait_vm_lgkm0<2 * PW>();
+            else if (en == 1) wait_vm_lgkm0<PW>();
+            else wait_vm_lgkm0<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
@@ -432,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void resunit128_kernel(ResUnitArgs u) {
     stage(0, 0);
     const int fr = lane & 15, fc = lane >> 4;
     for (int kt = 0; kt < nk; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BK);
@@ -453,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void resunit128_kernel(ResUnitArgs u) {
         }
     }
     // all waves done reading the ring; reuse it: [y_s k 0..63 | y_s k 64..127 | W2 k 0..63 | W2 k 64..127]
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     char *ys = lds;                 // 2 × 16 KiB
@@ -488,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void resunit128_kernel(ResUnitArgs u) {
             acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     // k=1 GEMM: K = 128 = 2 halves × 2 k-steps
@@ -641,10 +620,10 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void conv7_kernel(Conv
         const bool w1 = C7::WSLOTS == 3 && kt + 1 < nk;
         const bool wn1 = (kt >= 1 && (kt - 1) % 7 == 0 && (kt - 1) / 7 + 1 < nch) ||
                          (C7::WSLOTS == 3 && kt >= 2 && (kt - 2) % 7 == 0 && (kt - 2) / 7 + 1 < nch);
-        if (w1 && wn1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C7::PW + C7::PWIN) : "memory");
-        else if (w1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C7::PW) : "memory");
-        else if (wn1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C7::PWIN) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        if (w1 && wn1) wait_vm_lgkm0<C7::PW + C7::PWIN>();
+        else if (w1) wait_vm_lgkm0<C7::PW>();
+        else if (wn1) wait_vm_lgkm0<C7::PWIN>();
+        else wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (kt + C7::WSLOTS - 1 < nk)
@@ -692,7 +671,7 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void conv7_kernel(Conv
         }
     } else {
         // residual unit tail (C = 128): every wave done with the window / ring
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         constexpr int YH = BM * 128;    // y_s image: 2 k-halves × [BM rows][128 B]
@@ -729,7 +708,7 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void conv7_kernel(Conv
                 acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         // k=1 GEMM: K = 128 = 2 halves × 2 k-steps
@@ -803,19 +782,9 @@ constexpr int NPW = (WROWS + 7) / 8;   // 23 window pieces (8 rows) per chunk; t
 static_assert(LDS <= 81920, "two blocks per CU");
 }  // namespace ru
 
-// The kernel's LDS-DMA is inline asm (global_load_lds, saddr form: SGPR
-// base + one 32-bit VGPR lane offset) with explicit counted waits:
-//  * the builtin LDS-DMA forms either build a 64-bit VGPR address per piece (46 window + 16 W
-//    pieces per tile: hoisted and spilled, and every spill reload waits vmcnt(0)) or, for
-//    the buffer form, make the compiler wait vmcnt(0) before every LDS read;
-//  * the compiler, not seeing these loads, inserts no vmcnt waits for them (the x loads,
-//    which fill registers, stay compiler-visible).
-// M0 (the LDS destination) is set in the same asm; nothing else in this kernel uses M0.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void ru_dma(const char *base, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base)
-                 : "memory");
-}
+// The kernel's LDS-DMA is the asm saddr form (glds16_s, common.h) with explicit counted waits: of
+// the builtin form's 64-bit VGPR addresses, 46 window + 16 W pieces per tile would be hoisted
+// and spilled.  The x loads, which fill registers, stay compiler-visible.
 
 // window pieces [P0, P1) (8 rows each) of 64-channel chunk cc for the tile at m0, from input
 // row m0 − 3d + 8·P0 (≥ −27, and ≤ L_in + 181 at the end: the input carries zero rows in
@@ -827,7 +796,7 @@ __device__ __forceinline__ void ru_win(const ConvArgs &a, uint32_t buf, int64_t 
 #pragma unroll
     for (int q = P0; q < P1; ++q) {
         if (q * 8 + 8 <= ru::WROWS || (lane >> 3) < ru::WROWS - q * 8)
-            ru_dma(base, buf + q * 1024, voff + (q - P0) * 2048);
+            glds16_s(base, voff + (q - P0) * 2048, buf + q * 1024);
     }
 }
 
@@ -842,9 +811,9 @@ __device__ __forceinline__ void ru_w(const ResUnitArgs &u, uint32_t slot, int kt
         if (q < 16) {
             if (kt < 14) {
                 const int cc = kt >= 7 ? 1 : 0, tap = kt - 7 * cc;
-                ru_dma((const char *)u.c1.W + q * 8 * 1792 + tap * 256 + cc * 128, slot + q * 1024, voff1);
+                glds16_s((const char *)u.c1.W + q * 8 * 1792 + tap * 256 + cc * 128, voff1, slot + q * 1024);
             } else {
-                ru_dma((const char *)u.W2p + q * 8 * 256 + (kt - 14) * 128, slot + q * 1024, voff2);
+                glds16_s((const char *)u.W2p + q * 8 * 256 + (kt - 14) * 128, voff2, slot + q * 1024);
             }
         }
     }
@@ -863,9 +832,8 @@ __global__ __launch_bounds__(256, 2) void ru7_kernel(ResUnitArgs u, int64_t ntil
     const int64_t t0 = ntiles * blockIdx.x / gridDim.x, t1 = ntiles * (blockIdx.x + 1) / gridDim.x;
     if (t0 >= t1) return;
     // parameters first: their per-lane reads then fold into the 16-bit ds offset field
-    // parameters first: their per-lane reads then fold into the 16-bit ds offset field
     char *par = lds, *win = lds + ru::PAR, *wr = win + 2 * WINB;
-    const uint32_t win3 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)lds + ru::PAR;
+    const uint32_t win3 = lds_addr(lds) + ru::PAR;
     const uint32_t wr3 = win3 + 2 * WINB;                                 // LDS-DMA destinations
     float *psa2 = (float *)par, *psib2 = psa2 + 128, *psan = psa2 + 256, *psibn = psa2 + 384;
     bf16_t *pb1 = (bf16_t *)(par + 2048), *pb2 = (bf16_t *)(par + 2304);
@@ -874,7 +842,7 @@ __global__ __launch_bounds__(256, 2) void ru7_kernel(ResUnitArgs u, int64_t ntil
         psan[tid] = u.sa_next[tid]; psibn[tid] = u.sib_next[tid];
         pb1[tid] = a.bias[tid]; pb2[tid] = u.b2[tid];
     }
-    __builtin_amdgcn_s_waitcnt(0x0070);          // parameter loads retired before the first DMA
+    __builtin_amdgcn_s_waitcnt(waitcnt_enc(0, 0));   // parameter loads retired before the first DMA
     // DMA lane offsets: row lane>>3 of a piece, 16-B chunk swizzled by row & 7 (= lane>>3)
     const int l3 = lane >> 3, lc = ((lane & 7) ^ l3) * 16;
     const uint32_t vw0 = l3 * 256 + lc, vw1 = vw0 + 128;          // window chunk 0 / 1
@@ -904,12 +872,12 @@ __global__ __launch_bounds__(256, 2) void ru7_kernel(ResUnitArgs u, int64_t ntil
             // W waves: W(kt) (issued at kt−1) retired; younger only x (issued at 14 after W(15)).
             // Wave 3: chunk 0 (K-tile 0; younger: chunk 1's first 8 pieces) or chunk 1 (K-tile 7).
             if (!dma) {
-                if (kt == 15) __builtin_amdgcn_s_waitcnt(0x0078);       // vmcnt(8) lgkmcnt(0)
-                else __builtin_amdgcn_s_waitcnt(0x0070);
+                if (kt == 15) __builtin_amdgcn_s_waitcnt(waitcnt_enc(8, 0));
+                else __builtin_amdgcn_s_waitcnt(waitcnt_enc(0, 0));
             } else {
-                if (kt == 0) __builtin_amdgcn_s_waitcnt(0x0078);
-                else if (kt == 7) __builtin_amdgcn_s_waitcnt(0x0070);
-                else __builtin_amdgcn_s_waitcnt(0xC07F);                // lgkmcnt(0) only
+                if (kt == 0) __builtin_amdgcn_s_waitcnt(waitcnt_enc(8, 0));
+                else if (kt == 7) __builtin_amdgcn_s_waitcnt(waitcnt_enc(0, 0));
+                else __builtin_amdgcn_s_waitcnt(waitcnt_enc(63, 0));   // lgkmcnt(0) only
             }
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -1015,13 +983,13 @@ __global__ __launch_bounds__(256, 2) void ru7_kernel(ResUnitArgs u, int64_t ntil
         // loop-carried (they would pin 64 VGPRs through the whole K loop)
 #pragma unroll 1
         for (int kt = 0; kt < 12; kt += 2) {
-            ktile(kt, std::integral_constant<int, 0>{});
-            ktile(kt + 1, std::integral_constant<int, 1>{});
+            ktile(kt, IC<0>{});
+            ktile(kt + 1, IC<1>{});
         }
-        ktile(12, std::integral_constant<int, 0>{});
-        ktile(13, std::integral_constant<int, 1>{});
-        ktile(14, std::integral_constant<int, 0>{});
-        ktile(15, std::integral_constant<int, 1>{});
+        ktile(12, IC<0>{});
+        ktile(13, IC<1>{});
+        ktile(14, IC<0>{});
+        ktile(15, IC<1>{});
         // epilogue 2: x' = x + bf16(acc + b2) (raw, optional) and snake_next(x') → out_s.
         // (x is a compiler-visible load: an asm load's destination registers may be copied by
         // the register allocator before an asm wait retires them; the compiler's own wait
@@ -1083,15 +1051,6 @@ __global__ __launch_bounds__(256, 2) void ru7_kernel(ResUnitArgs u, int64_t ntil
 // before it have landed (vmcnt retires in order), and every chunk a K-tile reads was issued
 // before the W that K-tile's barrier waits for.
 // LDS: 2 560 (parameters) + 2 × 39 680 (windows: 310 rows × 64 channels) + 3 × 16 KiB = 128 KiB.
-template <int V>
-using IC7 = std::integral_constant<int, V>;
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void sfor(F &&f) {     // compile-time unrolled loop (f gets an integral_constant)
-    if constexpr (I0 < I1) {
-        f(std::integral_constant<int, I0>{});
-        sfor<I0 + 1, I1>(f);
-    }
-}
 namespace ru8 {
 // W ring distance: W(kt + D) is issued behind barrier kt into the slot of K-tile kt − 1 (D + 1
 // slots).  Measured (tools/ab_vae.py, one process, bit-identical): D = 3 (4 slots) 39.93 vs 39.90
@@ -1156,13 +1115,6 @@ __host__ __device__ constexpr int w_newer(int kt, bool more) {
 // the DMA schedule above
 }  // namespace ru8
 
-// vmcnt(N) with N a template constant (N ≤ 63)
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt field");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // helper h's window pieces q ∈ [P0, P1), q ≡ h (mod 2), of 64-channel chunk cc for the tile at m0
 template <int P0, int P1>
 __device__ __forceinline__ void ru8_win(const ConvArgs &a, uint32_t buf, int64_t m0, uint32_t voff, int lane, int h) {
@@ -1172,7 +1124,7 @@ __device__ __forceinline__ void ru8_win(const ConvArgs &a, uint32_t buf, int64_t
     for (int q = P0; q < P1; ++q) {
         if ((q & 1) != h) continue;
         if (q * 8 + 8 <= ru8::WROWS || (lane >> 3) < ru8::WROWS - q * 8)
-            ru_dma(base + q * 8 * 256, buf + q * 1024, voff);
+            glds16_s(base + q * 8 * 256, voff, buf + q * 1024);
     }
 }
 // helper h's 8 pieces (q ≡ h mod 2) of W K-tile kt into the ring slot at LDS address `slot`
@@ -1187,9 +1139,9 @@ __device__ __forceinline__ void ru8_w(const ResUnitArgs &u, uint32_t slot, int k
         const int q = h + 2 * i;
         if (kt < 14) {
             const int cc = kt >= 7 ? 1 : 0, tap = kt - 7 * cc;
-            ru_dma(w1 + q * 8 * 1792 + tap * 256 + cc * 128, slot + q * 1024, voff1);
+            glds16_s(w1 + q * 8 * 1792 + tap * 256 + cc * 128, voff1, slot + q * 1024);
         } else {
-            ru_dma(w2 + q * 8 * 256 + (kt - 14) * 128, slot + q * 1024, voff2);
+            glds16_s(w2 + q * 8 * 256 + (kt - 14) * 128, voff2, slot + q * 1024);
         }
     }
 }
@@ -1307,7 +1259,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
     const int64_t t0 = ntiles * blockIdx.x / gridDim.x, t1 = ntiles * (blockIdx.x + 1) / gridDim.x;
     if (t0 >= t1) return;
     char *par = lds, *win = lds + ru8::PAR, *wr = win + 2 * WINB;
-    const uint32_t win3 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)lds + ru8::PAR;
+    const uint32_t win3 = lds_addr(lds) + ru8::PAR;
     const uint32_t wr3 = win3 + 2 * WINB;
     float *psa2 = (float *)par, *psib2 = psa2 + 128, *psan = psa2 + 256, *psibn = psa2 + 384;
     bf16_t *pb1 = (bf16_t *)(par + 2048), *pb2 = (bf16_t *)(par + 2304);
@@ -1327,8 +1279,8 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
             sfor<0, 16>([&](auto KT) __attribute__((always_inline)) {
                 constexpr int kt = decltype(KT)::value;
                 if (t == t0 + 1) RU8_STAMP(1, 2 * kt, ru8_now());
-                if (more) vm_wait<ru8::w_newer(kt, true)>();
-                else vm_wait<ru8::w_newer(kt, false)>();
+                if (more) wait_vm<ru8::w_newer(kt, true)>();
+                else wait_vm<ru8::w_newer(kt, false)>();
                 if (t == t0 + 1) RU8_STAMP(1, 2 * kt + 1, ru8_now());
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
@@ -1343,7 +1295,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                 slot = slot + 1 == ru8::NSLOT ? 0 : slot + 1;
             });
         }
-        vm_wait<0>();
+        wait_vm<0>();
         RU8_STAMP_FLUSH(1);
         return;
     }
@@ -1385,7 +1337,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                 sfor<0, 16>([&](auto KT) __attribute__((always_inline)) {
                     constexpr int kt = decltype(KT)::value, PB = kt & 1;
                     if (H == 0 && t == t0 + 1) RU8_STAMP(2, 2 * kt, ru8_now());
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's LDS writes landed
+                    wait_lgkm0();   // this wave's LDS writes landed
                     if (H == 0 && t == t0 + 1) RU8_STAMP(2, 2 * kt + 1, ru8_now());
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");
@@ -1396,11 +1348,11 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                     // finish step kt − 2's pieces (Snake, LDS) first: they sit in ld[PB], the
                     // registers step kt issues into next — two steps for their rows to arrive
                     if constexpr (kt >= 2 && kt <= 5) {          // chunk 1 of this tile
-                        if (!first) fin(IC7<ru8::c1b_lo(kt - 2)>{}, IC7<ru8::c1b_hi(kt - 2)>{}, IC7<1>{}, IC7<PB>{});
+                        if (!first) fin(IC<ru8::c1b_lo(kt - 2)>{}, IC<ru8::c1b_hi(kt - 2)>{}, IC<1>{}, IC<PB>{});
                     } else if constexpr (kt >= 9 && kt <= 14) {  // chunk 0 of the next tile
-                        if (more) fin(IC7<ru8::c0_lo(kt - 9)>{}, IC7<ru8::c0_hi(kt - 9)>{}, IC7<0>{}, IC7<PB>{});
+                        if (more) fin(IC<ru8::c0_lo(kt - 9)>{}, IC<ru8::c0_hi(kt - 9)>{}, IC<0>{}, IC<PB>{});
                     } else if constexpr (kt <= 1) {              // issued at steps 14 / 15 of the previous tile
-                        if (!first) fin(IC7<ru8::c1a_lo(kt)>{}, IC7<ru8::c1a_hi(kt)>{}, IC7<1>{}, IC7<PB>{});
+                        if (!first) fin(IC<ru8::c1a_lo(kt)>{}, IC<ru8::c1a_hi(kt)>{}, IC<1>{}, IC<PB>{});
                     }
                     // issue step kt's loads into ld[PB] (the ranges of the DMA schedule)
                     if constexpr (kt <= 3) {
@@ -1412,12 +1364,12 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                     }
                 });
             }
-            vm_wait<0>();
+            wait_vm<0>();
             if (H == 0) RU8_STAMP_FLUSH(2);
         };
-        if (wave == 5) run(IC7<0>{});
-        else if (wave == 6) run(IC7<1>{});
-        else run(IC7<2>{});
+        if (wave == 5) run(IC<0>{});
+        else if (wave == 6) run(IC<1>{});
+        else run(IC<2>{});
         return;
     }
     if (!SIN && wave >= 4) {
@@ -1442,19 +1394,19 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                 // pre-barrier kt: W(kt) and everything issued before it landed
                 if (h == 0) {
                     if (first) {
-                        if (more) vm_wait<ru8::allowed(kt, 0, true, true)>();
-                        else vm_wait<ru8::allowed(kt, 0, true, false)>();
+                        if (more) wait_vm<ru8::allowed(kt, 0, true, true)>();
+                        else wait_vm<ru8::allowed(kt, 0, true, false)>();
                     } else {
-                        if (more) vm_wait<ru8::allowed(kt, 0, false, true)>();
-                        else vm_wait<ru8::allowed(kt, 0, false, false)>();
+                        if (more) wait_vm<ru8::allowed(kt, 0, false, true)>();
+                        else wait_vm<ru8::allowed(kt, 0, false, false)>();
                     }
                 } else {
                     if (first) {
-                        if (more) vm_wait<ru8::allowed(kt, 1, true, true)>();
-                        else vm_wait<ru8::allowed(kt, 1, true, false)>();
+                        if (more) wait_vm<ru8::allowed(kt, 1, true, true)>();
+                        else wait_vm<ru8::allowed(kt, 1, true, false)>();
                     } else {
-                        if (more) vm_wait<ru8::allowed(kt, 1, false, true)>();
-                        else vm_wait<ru8::allowed(kt, 1, false, false)>();
+                        if (more) wait_vm<ru8::allowed(kt, 1, false, true)>();
+                        else wait_vm<ru8::allowed(kt, 1, false, false)>();
                     }
                 }
                 if (h == 0 && t == t0 + 1) RU8_STAMP(1, 2 * kt + 1, ru8_now());
@@ -1476,7 +1428,7 @@ __global__ __launch_bounds__(SIN ? 320 + 64 * ru8::NWH : 384, 1) void ru8_kernel
                 slot = slot + 1 == ru8::NSLOT ? 0 : slot + 1;
             });
         }
-        vm_wait<0>();
+        wait_vm<0>();
         if (h == 0) RU8_STAMP_FLUSH(1);
         return;
     }
@@ -1890,15 +1842,17 @@ bool use_convp(const ConvArgs &a, int phases) {
 // C = 128 residual units: ACEHIP_RU7=2 (default) ru8_kernel, 1 ru7_kernel, 0 conv7_kernel<FUSED> (A/B)
 bool use_ru7() { return knobs().ru7 != 0; }
 
-int num_cus_conv() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
+// launch(RES, RAW, SN) with the integral constants of a conv's epilogue: a residual or none; the
+// raw output, the Snake output or both
+template <typename F>
+void with_epilogue(bool res, bool raw, bool sn, F &&launch) {
+    auto outs = [&](auto RES) {
+        if (raw && sn) launch(RES, std::true_type{}, std::true_type{});
+        else if (raw) launch(RES, std::true_type{}, std::false_type{});
+        else launch(RES, std::false_type{}, std::true_type{});
+    };
+    if (res) outs(std::true_type{});
+    else outs(std::false_type{});
 }
 
 }  // namespace
@@ -1917,22 +1871,27 @@ int conv_gemm(const ConvArgs &a, int phases, hipStream_t s) {
     if (!a.out && !a.out_s) return fail(-1, "conv_gemm: no output");
     if (!a.zero) return fail(-1, "conv_gemm: zero page");
     if (a.out_s && (!a.sa || !a.sib)) return fail(-1, "conv_gemm: snake params");
+    // the conv as an implicit GEMM on the two-phase ping-pong tile (256 × 256, eight waves; gemm.hip
+    // EPI_CONV): `taps` taps `dil` rows apart from row offset a0; column n is channel n % Cout of
+    // output row m·ostride + ooff + n / Cout
+    auto as_gemm = [&](int taps, int dil, int a0, int ostride, int ooff) {
+        GemmArgs g{};
+        g.A = a.in; g.lda = a.Cin;
+        g.W = a.W; g.ldw = taps * a.Cin;
+        g.C = a.out; g.Cs = a.out_s; g.ldc = a.N;
+        g.M = (int)a.M; g.N = ostride * a.N; g.K = taps * a.Cin;
+        g.epi = EPI_CONV; g.bias = a.bias; g.sa = a.sa; g.sib = a.sib;
+        g.conv_cin = a.Cin; g.conv_dil = dil; g.conv_a0 = a0;
+        g.conv_ostride = ostride; g.conv_ooff = ooff; g.conv_cout = a.N; g.conv_lout = a.L_out;
+        return g;
+    };
     const bool k7 = phases == 1 && a.taps == 7 && a.a_stride == 1 && a.c_stride == 1 && a.c_off == 0 &&
                     a.a_off == -3 * a.dil && a.dil <= 9 && a.L_out == a.M && a.L_in == a.M && !a.res && !a.out && a.out_s;
     if (k7 && knobs().conv7 == 2 && a.in_halo && a.N % 256 == 0 && 3 * a.dil <= kActPadRows && a.M < (1ll << 31)) {
-        // the k = 7 conv as an implicit GEMM on the two-phase ping-pong tile (256 × 256, eight
-        // waves; gemm.hip EPI_CONV): its halo rows come from the buffer's zero rows — the front
-        // ones are never written, the back ones are cleared here
+        // the k = 7 conv (k7: no raw output): its halo rows come from the buffer's zero rows — the
+        // front ones are never written, the back ones are cleared here
         HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * a.Cin), 0, (size_t)3 * a.dil * a.Cin * 2, s));
-        GemmArgs g{};
-        g.A = a.in; g.lda = a.Cin;
-        g.W = a.W; g.ldw = 7 * a.Cin;
-        g.Cs = a.out_s; g.ldc = a.N;
-        g.M = (int)a.M; g.N = a.N; g.K = 7 * a.Cin;
-        g.epi = EPI_CONV; g.bias = a.bias; g.sa = a.sa; g.sib = a.sib;
-        g.conv_cin = a.Cin; g.conv_dil = a.dil; g.conv_a0 = -3 * a.dil;
-        g.conv_ostride = 1; g.conv_ooff = 0; g.conv_cout = a.N; g.conv_lout = a.L_out;
-        return gemm_conv(g, s);
+        return gemm_conv(as_gemm(7, a.dil, -3 * a.dil, 1, 0), s);
     }
     // ConvTranspose1d (stride s, kernel 2s): the s phases' two-tap GEMMs side by side along N
     // (N = s·Cout, A — input rows m − 1 and m — read once for all of them), column n → channel
@@ -1941,29 +1900,14 @@ int conv_gemm(const ConvArgs &a, int phases, hipStream_t s) {
         a.c_stride == phases && a.M == a.L_in + 1 && !a.res && (int64_t)phases * a.N % 256 == 0 &&
         a.w_pstride == (int64_t)a.N * 2 * a.Cin && a.M < (1ll << 31)) {
         HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * a.Cin), 0, (size_t)a.Cin * 2, s));
-        GemmArgs g{};
-        g.A = a.in; g.lda = a.Cin;
-        g.W = a.W; g.ldw = 2 * a.Cin;
-        g.C = a.out; g.Cs = a.out_s; g.ldc = a.N;
-        g.M = (int)a.M; g.N = phases * a.N; g.K = 2 * a.Cin;
-        g.epi = EPI_CONV; g.bias = a.bias; g.sa = a.sa; g.sib = a.sib;
-        g.conv_cin = a.Cin; g.conv_dil = 1; g.conv_a0 = -1;
-        g.conv_ostride = phases; g.conv_ooff = a.c_off; g.conv_cout = a.N; g.conv_lout = a.L_out;
-        return gemm_conv(g, s);
+        return gemm_conv(as_gemm(2, 1, -1, phases, a.c_off), s);
     }
     // k = 1 convs (the C ≥ 256 residual units' second conv, with the residual) as a plain GEMM on
     // the ping-pong tile (ACEHIP_CONVP=3)
     if (knobs().convp == 3 && phases == 1 && a.taps == 1 && a.a_stride == 1 && a.a_off == 0 && a.c_stride == 1 &&
         a.c_off == 0 && a.L_in == a.M && a.L_out == a.M && a.N % 256 == 0 && a.M < (1ll << 31)) {
-        GemmArgs g{};
-        g.A = a.in; g.lda = a.Cin;
-        g.W = a.W; g.ldw = a.Cin;
-        g.C = a.out; g.Cs = a.out_s; g.ldc = a.N;
+        GemmArgs g = as_gemm(1, 1, 0, 1, 0);
         g.res = a.res; g.ldr = a.N;
-        g.M = (int)a.M; g.N = a.N; g.K = a.Cin;
-        g.epi = EPI_CONV; g.bias = a.bias; g.sa = a.sa; g.sib = a.sib;
-        g.conv_cin = a.Cin; g.conv_dil = 1; g.conv_a0 = 0;
-        g.conv_ostride = 1; g.conv_ooff = 0; g.conv_cout = a.N; g.conv_lout = a.L_out;
         return gemm_conv(g, s);
     }
     if (use_conv7() && k7) {
@@ -1975,29 +1919,20 @@ int conv_gemm(const ConvArgs &a, int phases, hipStream_t s) {
     }
     const int64_t tiles = ((a.M + BM - 1) / BM) * (a.N / BN);
     if (tiles >= (1ll << 31)) return fail(-1, "conv_gemm: grid too large");
+    const bool rs = a.res != nullptr, raw = a.out != nullptr, sn = a.out_s != nullptr;
     if (use_convp(a, phases) && a.taps * a.Cin / BK >= 3 && a.N <= cp::MAXN) {   // ≥ 3 K-tiles per item (vmcnt bookkeeping)
         const int64_t items = tiles * phases;
-        const int nb = (int)std::min<int64_t>(items, num_cus_conv());
-        const bool rs = a.res != nullptr, raw = a.out != nullptr, sn = a.out_s != nullptr;
-#define L(R, W, S) convp_kernel<R, W, S><<<nb, 512, 0, s>>>(a, items, phases)
-        if (rs) {
-            if (raw && sn) L(true, true, true); else if (raw) L(true, true, false); else L(true, false, true);
-        } else {
-            if (raw && sn) L(false, true, true); else if (raw) L(false, true, false); else L(false, false, true);
-        }
-#undef L
+        const int nb = (int)std::min<int64_t>(items, device_cus());
+        with_epilogue(rs, raw, sn, [&](auto RES, auto RAW, auto SN) {
+            convp_kernel<RES.value, RAW.value, SN.value><<<nb, 512, 0, s>>>(a, items, phases);
+        });
         HIP_TRY(hipGetLastError());
         return 0;
     }
     dim3 grid((unsigned)tiles, phases);
-    const bool rs = a.res != nullptr, raw = a.out != nullptr, sn = a.out_s != nullptr;
-#define L(R, W, S) conv_gemm_kernel<R, W, S><<<grid, 256, 0, s>>>(a)
-    if (rs) {
-        if (raw && sn) L(true, true, true); else if (raw) L(true, true, false); else L(true, false, true);
-    } else {
-        if (raw && sn) L(false, true, true); else if (raw) L(false, true, false); else L(false, false, true);
-    }
-#undef L
+    with_epilogue(rs, raw, sn, [&](auto RES, auto RAW, auto SN) {
+        conv_gemm_kernel<RES.value, RAW.value, SN.value><<<grid, 256, 0, s>>>(a);
+    });
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2006,11 +1941,13 @@ int resunit128(const ResUnitArgs &u, hipStream_t s) {
     const ConvArgs &a = u.c1;
     if (a.Cin != 128 || a.N != 128 || a.taps != 7 || !a.zero || !a.bias || !a.sa) return fail(-1, "resunit128: args");
     if (u.x == u.out_s || a.in == u.out_s) return fail(-1, "resunit128: out_s must not alias x / x_s");
-    if (u.snake_in && !(knobs().ru7 == 2 && u.W2p && u.in_zero_pad && a.dil <= 9 && a.a_off == -3 * a.dil && a.L_in == a.M))
-        return fail(-1, "resunit128: snake_in runs on ru8_kernel only");
-    if (knobs().ru7 == 2 && u.W2p && u.in_zero_pad && a.dil <= 9 && a.a_off == -3 * a.dil && a.L_in == a.M) {
+    // what ru8_kernel and ru7_kernel take: the permuted W2, a "same" k = 7 conv, its halo in the
+    // input's zero rows
+    const bool padded7 = u.W2p && u.in_zero_pad && a.dil <= 9 && a.a_off == -3 * a.dil && a.L_in == a.M;
+    if (u.snake_in && !(knobs().ru7 == 2 && padded7)) return fail(-1, "resunit128: snake_in runs on ru8_kernel only");
+    if (knobs().ru7 == 2 && padded7) {
         const int64_t nt = (a.M + ru8::BM - 1) / ru8::BM;
-        const int nb = (int)std::min<int64_t>(nt, (int64_t)num_cus_conv());
+        const int nb = (int)std::min<int64_t>(nt, (int64_t)device_cus());
         HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * 128), 0, (size_t)kActPadRows * 256, s));
         if (!u.snake_in || !u.keep_raw) {
             if (!u.out_s || !u.sa_next || !u.sib_next) return fail(-1, "resunit128: out_s and the next Snake's parameters");
@@ -2028,9 +1965,9 @@ int resunit128(const ResUnitArgs &u, hipStream_t s) {
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (use_ru7() && u.W2p && u.in_zero_pad && a.dil <= 9 && a.a_off == -3 * a.dil && a.L_in == a.M) {
+    if (use_ru7() && padded7) {
         const int64_t nt = (a.M + ru::BM - 1) / ru::BM;
-        const int nb = (int)std::min<int64_t>(nt, 2 * (int64_t)num_cus_conv());
+        const int nb = (int)std::min<int64_t>(nt, 2 * (int64_t)device_cus());
         // the k=7 halo past the end reads kActPadRows zero rows behind the input
         HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * 128), 0, (size_t)kActPadRows * 256, s));
         if (u.keep_raw) ru7_kernel<true><<<nb, 256, 0, s>>>(u, nt);

@@ -84,14 +84,13 @@ inline void klaunch(void (*kern)(KArgs...), dim3 grid, dim3 block, hipStream_t s
         kern<<<grid, block, 0, s>>>(args...);
     }
 }
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // own LDS-DMAs retired down to N outstanding + own LDS reads retired, then a
 // raw barrier (no implicit vmcnt(0)) and a compiler fence so no LDS access
 // moves across it
 template <int N>
 __device__ __forceinline__ void ring_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+    wait_vm_lgkm0<N>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
@@ -337,7 +336,7 @@ __global__ __launch_bounds__(WM *WN * 64 + 64 * NH, 1) void gemm_kernel(GemmArgs
                 else ring_barrier<0>();
                 if (kt + STAGES - 1 < nk) hst((kt + STAGES - 1) % STAGES, (kt + STAGES - 1) * BK);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             return;
         }
     }
@@ -629,14 +628,6 @@ struct PPSrcPtr {
     __device__ __forceinline__ void dmaB(int i, int k0, char *dst) const { glds16(pb[i] + k0, dst); }
 };
 
-// LDS-DMA of one 1 KiB piece in the saddr form (SGPR base, 32-bit per-lane offset), as
-// attention.hip's pw_dma; M0 (the LDS destination) is written in the same statement
-__device__ __forceinline__ void glds16_s(const char *sbase, uint32_t voff, char *lds_dst) {
-    const uint32_t la = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char *)lds_dst;
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(la), "v"(voff), "s"(sbase)
-                 : "memory");
-}
-
 // The same addresses as a wave-uniform tile base (scalar registers: the tile origin is the
 // same for every lane) + 32-bit per-lane byte offsets.  A tile walk derives the next tile's set
 // from scalars after the K loop instead of holding a second set of 64-bit pointers across it.
@@ -657,9 +648,11 @@ struct PPSrcOff {
 #pragma unroll
         for (int i = 0; i < NA; ++i) oa[i] = pp_off_a(a.M, a.lda, m0, wave, lane, i);
     }
-    __device__ __forceinline__ void dmaA(int i, int k0, char *dst) const { glds16_s(ba + (int64_t)k0 * 2, oa[i], dst); }
+    __device__ __forceinline__ void dmaA(int i, int k0, char *dst) const {
+        glds16_s(ba + (int64_t)k0 * 2, oa[i], lds_addr(dst));
+    }
     __device__ __forceinline__ void dmaB(int i, int k0, char *dst) const {
-        glds16_s(bb + (uint64_t)i * bstep + (int64_t)k0 * 2, ob, dst);
+        glds16_s(bb + (uint64_t)i * bstep + (int64_t)k0 * 2, ob, lds_addr(dst));
     }
 };
 
@@ -735,19 +728,19 @@ __device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src 
         stageA(0, 0);
         if (nk > 1) {
             stageB(1, BK);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
+            wait_vm<NB>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
     } else {
         if (pend < 0) pp_prologue_issue<BM, EPI>(a, lds, src, wave);
         __builtin_amdgcn_sched_barrier(0);
         if (pend > 0) {
-            if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB + PP_SWIGLU_STORES) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PP_SWIGLU_STORES) : "memory");
+            if (nk > 1) wait_vm<NB + PP_SWIGLU_STORES>();
+            else wait_vm<PP_SWIGLU_STORES>();
         } else {
-            if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (nk > 1) wait_vm<NB>();
+            else wait_vm<0>();
         }
     }
     bar();
@@ -784,7 +777,7 @@ __device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src 
             for (int ks = 0; ks < 2; ++ks) bf[j][ks] = *(const bf16x8 *)(b + swz(brow + j * 16 + fr, ks * 4 + fc));
         readA(b, 0);
         if (kt + 1 < nk) stageA((kt + 1) & 1, (kt + 1) * BK);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         bar();
         mma(0);
         bar();
@@ -793,9 +786,9 @@ __device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src 
         readA(b, 1);
         if (kt + 2 < nk) {
             stageB(kt & 1, (kt + 2) * BK);
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NB) : "memory");
+            wait_vm_lgkm0<NB>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            wait_vm_lgkm0<0>();
         }
         bar();
         mma(1);
@@ -867,7 +860,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
     pp_epilogue<BM, EPI>(a, lds, acc, m0, n0);
     if constexpr (EPI == EPI_HEADPOST) return;
 #ifdef GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
 #endif
     GSTAMP(3);
     GSTAMP_REAL(5);
@@ -938,7 +931,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, Gem
         pend = -1;
         pp_epilogue<128, EPI>(t, lds, acc, m0, n0);
 #ifdef GEMM_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
 #endif
         GSTAMP_AT(i, 3);
         GSTAMP_REAL_AT(i, 5);
@@ -1026,15 +1019,15 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
                 for (int i = 0; i < PPH; ++i) glds16(hs[i] + k0, lds + buf * STAGE + (h + NH * i) * 1024);
             };
             for (int t = 0; t < NS; ++t) fill(t, min(t, nk - 1) * BK);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * PPH) : "memory");
+            wait_vm<(NS - 1) * PPH>();
             __builtin_amdgcn_s_barrier();
             for (int kt = 0; kt < nk; ++kt) {
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * PPH) : "memory");   // tile kt+1 landed
+                wait_vm<(NS - 2) * PPH>();   // tile kt+1 landed
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 fill(kt % NS, min(kt + NS, nk - 1) * BK);
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             if constexpr (EPI == EPI_HEADPOST) {   // the head-post epilogue's two block barriers
                 __syncthreads();
                 __syncthreads();
@@ -1089,7 +1082,7 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
     // every read before it has retired and adds none after it
     constexpr int VM = (NS - 2) * PW;
     static_assert(VM < 64, "vmcnt field");
-    constexpr int WAIT_ENC = 0x0070 | (VM & 15) | ((VM >> 4) << 14);
+    constexpr int WAIT_ENC = waitcnt_enc(VM, 0);
     auto bar = [] {
         __builtin_amdgcn_s_waitcnt(WAIT_ENC);
         __builtin_amdgcn_s_barrier();
@@ -1112,7 +1105,7 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
         for (int t = 0; t < NS; ++t)
 #pragma unroll
             for (int i = 0; i < PW; ++i) stage1(t, min(t, nk - 1) * BK, i);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * PW) : "memory");
+        wait_vm<(NS - 1) * PW>();
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1123,7 +1116,7 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
     static_assert(FIRST + EVERY * (PW - 1) < SM * SN, "refill pieces must fit in half B");
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt % NS, nxt = (kt + 1) % NS;
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_s_waitcnt(waitcnt_enc(63, 0));
         rd(lds + cur * STAGE, 1, x1, w1);
         mm(x0, w0, none);
         bar();
@@ -1139,7 +1132,7 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
             mm(x1, w1, none);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     // the asm MFMAs are opaque to the hazard recognizer: let the last ones retire
     // before their accumulators are read
     GSTAMP(2);
@@ -1158,7 +1151,7 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
         epilogue_tile<SM, SN, EPI>(a, acc, m0 + wm * TM, n0 + wn * TN, fr, fc);
     }
 #ifdef GEMM_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
 #endif
     GSTAMP(3);
     GSTAMP_REAL(5);
@@ -1283,20 +1276,10 @@ bool gemm_ext_events(hipEvent_t start, hipEvent_t stop) {
     return consumed;
 }
 
-static int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
 // the CU count the tile planner (gemm_pick_variant, gemm_tail_split, the persistent grid) fills:
 // the device's, or fewer under ACEHIP_GEMM_CUS so tests reach multi-round grids at small shapes
 static int plan_cus() {
-    const int cap = knobs().gemm_cus, n = num_cus();
+    const int cap = knobs().gemm_cus, n = device_cus();
     return cap > 0 && cap < n ? cap : n;
 }
 
@@ -1316,7 +1299,7 @@ static int launch_pp_persist(const GemmArgs &hd, const GemmArgs &tl, int nmain, 
 // hot or cold weights (tools/bench_gemm.py, r02).
 static bool use_w4s(int64_t M, int N) {
     if (N % 128) return false;
-    const int cus = num_cus();
+    const int cus = device_cus();
     const int64_t t = ((M + 191) / 192) * (N / 128);
     return t <= cus && t * 4 >= (int64_t)cus * 3;
 }
@@ -1328,7 +1311,7 @@ static bool use_w4s(int64_t M, int N) {
 // Grids that fill at most half the chip fall back to 128×128 (2 blocks/CU): at
 // M = 3000, N = 2048 (the cross-O GEMM of the conditional rows) 37 µs vs 46 µs.
 int gemm_pick_variant(int64_t M, int N) {
-    if (use_w4s(M, N) && (N % 256 || ((M + 191) / 192) * (N / 256) <= num_cus() / 2)) return 13;
+    if (use_w4s(M, N) && (N % 256 || ((M + 191) / 192) * (N / 256) <= device_cus() / 2)) return 13;
     if (N % 256) return 0;
     const int cus = plan_cus();
     const int64_t t7 = ((M + 255) / 256) * (N / 256), t8 = ((M + 191) / 192) * (N / 256);
@@ -1504,8 +1487,8 @@ int gemm_conv(const GemmArgs &a, hipStream_t s) {
     // per CU) quadruple it.  10 s decode 2.13 → 1.96 (128) → 1.91 ms (64 below a quarter of the
     // chip), bit-identical (profiles/r05az_ab_vae_small_tiles.log)
     const int64_t t256 = (int64_t)((a.M + 255) / 256) * (a.N / 256);
-    if (t256 * 4 <= num_cus()) return launch_conv64(a, s);
-    if (t256 * 2 <= num_cus()) return launch_pp<128>(a, s);
+    if (t256 * 4 <= device_cus()) return launch_conv64(a, s);
+    if (t256 * 2 <= device_cus()) return launch_pp<128>(a, s);
     return launch_pp<256>(a, s);
 }
 
@@ -1534,7 +1517,7 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
     // weights: 26.1 → 19.0 µs (tools/bench_small_m.py).  ACEHIP_SMALLM_WHOLEK=0: split-K (A/B)
     if (a.epi == EPI_SWIGLU && a.M <= 128 && a.N % 64 == 0 && kn.smallm_wholek) return gemm_variant(a, kn.smallm_wholek == 2 ? 17 : 16, s);
     if (a.ws && a.N % 128 == 0 && a.K % BK == 0 && (a.N % 256 == 0 || a.epi != EPI_HEADPOST)) {
-        const int cus = num_cus();
+        const int cus = device_cus();
         const int64_t tiles = ((a.M + 127) / 128) * (a.N / 128);
         const int nk = a.K / BK;
         if (tiles * 2 <= cus && nk >= 8) {
@@ -1550,7 +1533,7 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
         // small grid outside the four-wave tile's geometry goes through the staging buffer +
         // the standalone head_post kernel on 128×128 tiles
         const int64_t t192 = (int64_t)((a.M + 191) / 192) * (a.N / 256);
-        const bool small = t192 * 2 <= num_cus();
+        const bool small = t192 * 2 <= device_cus();
         if (small && use_w4s(a.M, a.N)) return gemm_variant(a, 13, s);
         if (small && a.ws && (size_t)a.M * a.N * 2 <= a.ws_bytes) {
             GemmArgs st = a;
@@ -1569,7 +1552,7 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
         // the 192-row rounds (cost model of gemm_pick_variant, a 128×256 tile ≈ 0.6 of a 192×256
         // one): QKV at 240 s, 32 × 16 = 2 rounds of 192 → 1 round of 256 + 1 of 128
         if (kn.gemm_hp_tail && a.N % 256 == 0) {
-            const int cus = num_cus();
+            const int cus = device_cus();
             const int64_t nN = a.N / 256, t7 = ((a.M + 255) / 256) * nN, t8 = ((a.M + 191) / 192) * nN;
             const double c_split = (double)(t7 / cus) * 1.093 + 0.6, c8 = (double)((t8 + cus - 1) / cus);
             if (t7 >= cus && c_split < c8) {

@@ -36,6 +36,9 @@ struct Knobs {
     unsigned gen = 0;
 };
 const Knobs &knobs();
+// compute units of the current device (256 if the query fails), read once per process; every
+// planner puts its own policy on top (plan_cus, num_cus_attn, decode_cus)
+int device_cus();
 
 // ------------------------------------------------------------------ GEMM ---
 // per-head post-projection: q/k RMSNorm (+RoPE) and scatter to head-major layouts

@@ -1,6 +1,7 @@
 // knobs.hip — the library's A/B switches, read from the environment ONCE (first use, or
 // acehip_reload_knobs) instead of a getenv on every launch.  Defaults are the production
 // choice; DESIGN.md's appendix lists what each alternative measured.
+// The other process-wide value read once lives here too: the device's CU count (device_cus).
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
@@ -62,6 +63,17 @@ const Knobs &knobs() {
         }
     }
     return g_knobs;
+}
+
+int device_cus() {
+    static int n = 0;
+    if (!n) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+    }
+    return n;
 }
 
 }  // namespace acehip
