@@ -32,7 +32,7 @@ EXPORTS = [
     "acehip_wav_peak_normalize", "acehip_wav_postprocess", "acehip_wav_postprocess_pcm16",
     "acehip_gemm_bf16", "acehip_gemm_bf16_ex", "acehip_gemm_res_bf16", "acehip_gemm_res_norm_bf16",
     "acehip_attention_bf16",
-    "acehip_rmsnorm_bf16", "acehip_gemm_headpost_bf16", "acehip_attention_masked_bf16",
+    "acehip_rmsnorm_bf16", "acehip_gemm_headpost_bf16", "acehip_attention_masked_bf16", "acehip_cross_attn_bf16",
     "acehip_enc_create", "acehip_enc_set_weight", "acehip_enc_finalize", "acehip_enc_embed",
     "acehip_enc_forward", "acehip_enc_destroy", "acehip_fsq_quantize", "acehip_fsq_codes_from_indices",
     "acehip_attention_probs_bf16", "acehip_dit_forward_capture",
@@ -145,6 +145,8 @@ def _declare(lib):
         "acehip_rmsnorm_bf16": (c_int, [P, P, P, P, c_int64, c_int, P, c_int, c_int, c_float, c_int, P]),
         "acehip_gemm_headpost_bf16": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int,
                                               P, P, P, P, c_float, P, P, P, P]),
+        "acehip_cross_attn_bf16": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                           c_float, c_int, POINTER(c_int), P]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(lib, name):

@@ -39,6 +39,7 @@
 // hand-placed between the MFMAs (its header below has the schedule and the A/B numbers).
 #include <atomic>
 #include <type_traits>
+#include "attn_tile.h"
 #include "kernels.h"
 
 namespace acehip {
@@ -55,18 +56,9 @@ namespace {
 //     design) that ran attn_fwd_kernel without the QKᵀ MFMAs, the softmax VALU, the P·V MFMAs,
 //     the K/V LDS reads or the per-tile barrier; each was timed against the production build
 //     with tools/bench_attn.py to size that part of the tile, removed.
-constexpr float ATT_TAU = 8.0f;   // lazy-rescale threshold (0: rescale on every new max)
-
+// (ATT_TAU, KT, the mask sentinels NEG / PAST, the asm LDS reads and the tile swizzle kvoff live in
+// attn_tile.h with the per-wave tile body, shared with the fused cross-attention kernel of gemm.hip)
 constexpr int QB = 128;    // queries per workgroup
-constexpr int KT = 64;     // keys per tile
-// Sentinels are powers of two so that NEG·sl2 is exact: the exp2 argument
-// fmaf(NEG, sl2, −m) of a row whose max IS the sentinel is then exactly 0
-// (an all-masked row weighs its keys uniformly, and a row's all-masked first
-// tiles add finite garbage that the first real tile's rescale zeroes).  With a
-// non-power-of-two sentinel the fma's unrounded product differs from the
-// rounded max by up to half an ulp of 1e29 — exp2 of that is 0 or inf.
-constexpr float NEG = -0x1p100f;
-constexpr float PAST = -0x1p126f;   // masked mode: keys past Sk (never weighted, even in an all-masked row)
 
 // tail balancing: units [0, full) run whole; each later unit runs as nsplit
 // KV-range parts whose partial (O, m, l) meet in ws, merged by the last part
@@ -82,50 +74,6 @@ struct SplitArgs {
     // (2·grid slots); no workgroup waits for another, so residency of the grid is not assumed.
     int sk_total = 0, sk_nt = 0;
 };
-
-// ds_read_b64_tr_b16 by inline asm (see pv() for why not the builtin)
-__device__ __forceinline__ s16x4 ds_read_tr16(const char *lds_ptr) {
-    s16x4 r;
-    const uint32_t a = lds_addr(lds_ptr);
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(a));
-    return r;
-}
-
-__device__ __forceinline__ bf16x8 ds_read_b128(const char *lds_ptr) {
-    bf16x8 r;
-    const uint32_t a = lds_addr(lds_ptr);
-    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(a));
-    return r;
-}
-// LDS reads at (per-lane offset VGPR + compile-time immediate): the per-lane parts
-// (swizzled chunk offsets) are 8 VGPRs for K and 8 for V; the ring slot and the row
-// block are the instruction's 16-bit offset field (the tile loop is unrolled by the
-// two ring slots so both are constants) — no address VALU per read, and no hoisted
-// VGPR address per (slot, fragment), which had cost ~50 VGPRs and spills.
-template <int OFF>
-__device__ __forceinline__ bf16x8 ds_read_b128_imm(uint32_t lane_off) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-    bf16x8 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(lane_off), "n"(OFF));
-    return r;
-}
-template <int OFF>
-__device__ __forceinline__ s16x4 ds_read_tr16_imm(uint32_t lane_off) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
-    s16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lane_off), "n"(OFF));
-    return r;
-}
-// s_waitcnt lgkmcnt(0) that the listed fragments depend on (nothing using them can be
-// scheduled above it)
-__device__ __forceinline__ void lgkm_wait8(bf16x8 (&f)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]),
-                 "+v"(f[6]), "+v"(f[7]));
-}
-
-__device__ __forceinline__ int kvoff(int row, int ch) {
-    return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
-}
 
 // Tail-split / short-split hand-off of one wave's (or pw sub-block's) partial (O, m, l):
 // 16 KB of O as sixteen 1-KB lane-contiguous chunks (chunk k = O[k / 4][4(k % 4) .. +3] of
@@ -356,6 +304,10 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     // LDS byte address of the ring (uniform) and the per-lane swizzled offsets:
     // K fragment (row r [+32], logical chunk 2s+hh) — the swizzle depends on row & 15 only;
     // Vᵀ fragment (d-block dt, row 4(g>>1)+qq [+8]) — rows +16s, +32t are uniform offsets
+    // (attn_tile.h's attn_lane_offsets is the same formula; written out here as it always was:
+    // through the helper hipcc orders this kernel's instructions differently, and with it
+    // written out the kernel's assembly is the one it had before the tile body moved to the
+    // header, up to one register's number)
     const uint32_t lds_base = lds_addr(lds);
     uint32_t koff[8], voff[4][2];
 #pragma unroll
@@ -366,56 +318,6 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         for (int h8 = 0; h8 < 2; ++h8)
             voff[dt][h8] = lds_base + NBUF * TILE +
                            kvoff(4 * (g >> 1) + qq + 8 * h8, 4 * dt + 2 * (g & 1) + (pp >> 1)) + 8 * (pp & 1);
-    // Oᵀ[d][q] += Vᵀ·Pᵀ; Vᵀ fragments by transposed LDS reads.  The reads are issued by
-    // inline asm: hipcc's waitcnt pass treats its own ds_read_tr builtin as an LDS read
-    // that may alias the in-flight LDS-DMA refills and waits vmcnt(0) before it (every
-    // tile, draining the ring); the asm reads are waited explicitly (lgkmcnt(0) bound to
-    // their results, so no MFMA can move above the wait)
-    // VB: the V half of the ring slot (compile-time); key rows +32t +16s are immediates too
-    auto pv_reads = [&](auto VBC, int dt, s16x4 (&rd)[2][2][2]) {
-        constexpr int VB = decltype(VBC)::value;
-        rd[0][0][0] = ds_read_tr16_imm<VB>(voff[dt][0]);
-        rd[0][0][1] = ds_read_tr16_imm<VB>(voff[dt][1]);
-        rd[0][1][0] = ds_read_tr16_imm<VB + 16 * 256>(voff[dt][0]);
-        rd[0][1][1] = ds_read_tr16_imm<VB + 16 * 256>(voff[dt][1]);
-        rd[1][0][0] = ds_read_tr16_imm<VB + 32 * 256>(voff[dt][0]);
-        rd[1][0][1] = ds_read_tr16_imm<VB + 32 * 256>(voff[dt][1]);
-        rd[1][1][0] = ds_read_tr16_imm<VB + 48 * 256>(voff[dt][0]);
-        rd[1][1][1] = ds_read_tr16_imm<VB + 48 * 256>(voff[dt][1]);
-    };
-    auto pv_wait = [](s16x4 (&rd)[2][2][2]) {
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(rd[0][0][0]), "+v"(rd[0][0][1]), "+v"(rd[0][1][0]), "+v"(rd[0][1][1]),
-                       "+v"(rd[1][0][0]), "+v"(rd[1][0][1]), "+v"(rd[1][1][0]), "+v"(rd[1][1][1]));
-    };
-    auto pv_mfma = [&](int dt, const s16x4 (&rd)[2][2][2], const bf16x8 (&pf)[2][2]) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                // whole-vector reinterpretation (per-element bit_cast<__bf16> insertion
-                // is miscompiled by ROCm 7.2 hipcc: it keeps only the first dword)
-                const s16x8 cat = __builtin_shufflevector(rd[t][s][0], rd[t][s][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                const bf16x8 vf = __builtin_bit_cast(bf16x8, cat);
-                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[t][s], oacc[dt], 0, 0, 0);
-            }
-    };
-    // P·V: the reads of d-block dt+1 are in flight during the MFMAs of dt
-    auto pv = [&](auto VBC, const bf16x8 (&pf)[2][2]) {
-        s16x4 ra[2][2][2], rb[2][2][2];
-        pv_reads(VBC, 0, ra);
-        pv_wait(ra);
-        pv_reads(VBC, 1, rb);
-        pv_mfma(0, ra, pf);
-        pv_wait(rb);
-        pv_reads(VBC, 2, ra);
-        pv_mfma(1, rb, pf);
-        pv_wait(ra);
-        pv_reads(VBC, 3, rb);
-        pv_mfma(2, ra, pf);
-        pv_wait(rb);
-        pv_mfma(3, rb, pf);
-    };
 
     // end-of-tile wait: own DMAs of the next tile landed, own LDS reads retired; then the
     // barrier publishes the tile to every wave and retires the current tile's reads (WAR
@@ -426,7 +328,6 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
-    bf16x8 pf[2][2];          // P of the current tile (bf16), B operand of P·V
 
     // one tile; SLOT (compile-time: the loop is unrolled by the ring slots) is the ring
     // slot holding tile it, so every LDS address offset is an immediate
@@ -448,85 +349,20 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
             return;
         }
 
-        // Sᵀ tiles: keys 32t..32t+31 × this wave's 32 queries
-        // K fragments by asm reads (see pv()); the reads of key half t=1 are in flight
-        // during the MFMAs of t=0
-        f32x16 st[2];
-        {
-            bf16x8 k0[8], k1[8];
-#pragma unroll
-            for (int s = 0; s < 8; ++s) k0[s] = ds_read_b128_imm<KB>(koff[s]);
-            lgkm_wait8(k0);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) k1[s] = ds_read_b128_imm<KB + 32 * 256>(koff[s]);
-#pragma unroll
-            for (int j = 0; j < 16; ++j) { st[0][j] = 0.f; st[1][j] = 0.f; }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) st[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0[s], qf[s], st[0], 0, 0, 0);
-            lgkm_wait8(k1);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1[s], qf[s], st[1], 0, 0, 0);
-        }
-        // running max on raw scores (scale folded into the exp2 FMA below);
-        // interior tiles of full / cross attention need no mask
-        float mx = NEG;
-        if (interior) {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) mx = fmaxf(mx, st[t][j]);
-        } else {
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int kj = kv0 + 32 * t + (j & 3) + 8 * (j >> 2) + 4 * hh;
-                    // branch-free: window < 0 ⇒ wlim = INT_MAX
-                    const bool inr = kj < Sk;
-                    bool ok = inr & (abs(qi - kj) <= wlim) & (!causal | (kj <= qi));
-                    float bad = NEG;
-                    if (km) {   // key-padding mode (uniform over branches: km is kernel-uniform)
-                        ok = ok && km[inr ? kj : 0] != 0;
-                        bad = inr ? NEG : PAST;
-                    }
-                    const float sv = ok ? st[t][j] : bad;
-                    st[t][j] = sv;
-                    mx = fmaxf(mx, sv);
-                }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * sl2;
-        // lazy rescale: the running reference max moves only when a score exceeds it by more
-        // than ATT_TAU (log2 units), so P = 2^(s − m) ≤ 2^TAU and after the first tiles the
-        // O/l rescale (64 VALU per lane) is skipped almost always; O/l is the same softmax
-        const float mn = mx > m + ATT_TAU ? mx : m;
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);   // raw v_exp_f32 (no denormal range fix-up)
-        m = mn;
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(st[t][j], sl2, -mn));
-                st[t][j] = p;
-                rs += p;
+        // the shared per-wave tile body (attn_tile.h): Sᵀ = K·Qᵀ, online softmax, Oᵀ += Vᵀ·Pᵀ;
+        // the mask runs on tiles that are not interior only
+        attn_wave_tile<KB, VB>(qf, koff, voff, oacc, m, l, sl2, interior, [&](int t, int j, float sc) {
+            const int kj = kv0 + 32 * t + (j & 3) + 8 * (j >> 2) + 4 * hh;
+            // branch-free: window < 0 ⇒ wlim = INT_MAX
+            const bool inr = kj < Sk;
+            bool ok = inr & (abs(qi - kj) <= wlim) & (!causal | (kj <= qi));
+            float bad = NEG;
+            if (km) {   // key-padding mode (uniform over branches: km is kernel-uniform)
+                ok = ok && km[inr ? kj : 0] != 0;
+                bad = inr ? NEG : PAST;
             }
-        rs += __shfl_xor(rs, 32, 64);
-        l = l * alpha + rs;
-        if (__any(alpha != 1.0f)) {                  // skip the O rescale when no row's max grew
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) oacc[i][j] *= alpha;
-        }
-
-        // P (bf16) as the B operand: tile t, k-step s ← registers 8s..8s+7
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pf[t][s][j] = (__bf16)st[t][8 * s + j];
-        pv(IC<VB>{}, pf);
+            return ok ? sc : bad;
+        });
         tile_barrier();
     };
     if (ntiles > 0) stage_tile(t_first * KT, 0);
@@ -623,27 +459,8 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
         __syncthreads();                               // s_fold is reused by the next piece
     }
 
-    if (write_o && qi < Sq) {                 // both lanes of a row pair (lane, lane ^ 32) agree
-    const float inv = 1.0f / l;
-    bf16_t *op = o + ((int64_t)b * Sq + qi) * o_ld + hq * 128;
-    // lane (r, hh) holds columns 32dt + 8gg + 4hh .. +3 of its row; the two half-waves swap one
-    // 4-column group per pair (gg, gg+1) so each lane stores 8 contiguous columns as one 16-B
-    // store (the store tail is issue-bound: MI355X_MICROARCH "attention epilogue store tail")
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int gp = 0; gp < 2; ++gp) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float a0 = oacc[dt][8 * gp + j] * inv, a1 = oacc[dt][8 * gp + 4 + j] * inv;
-                const float got = __shfl_xor(hh ? a0 : a1, 32, 64);
-                v[j] = hh ? got : a0;
-                v[4 + j] = hh ? a1 : got;
-            }
-            *(uint4 *)(op + 32 * dt + 16 * gp + 8 * hh) = pack8(v);
-        }
-    }
+    if (write_o && qi < Sq)                   // both lanes of a row pair (lane, lane ^ 32) agree
+        attn_wave_store_o(oacc, l, o + ((int64_t)b * Sq + qi) * o_ld + hq * 128, hh);
     if (!streamk) break;
     g0 += ntiles;
     if (g0 >= g1) break;
@@ -1575,6 +1392,33 @@ size_t attention_ws_bytes() {
     const size_t cus = std::max<size_t>(1024, (size_t)num_cus_attn());
     // [tickets: cus ints][slabs: cus · 8 waves · 66·64 floats]; stream-K uses 2 slabs per workgroup
     return cus * 8 * 66 * 64 * sizeof(float) + cus * sizeof(int);   // ≤ cus split parts in flight
+}
+
+// mirrors attention()'s choices below for window < 0 and no mask
+bool attention_whole_units(int B, int H, int KV, int Sq, int Sk, bool have_ws) {
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || KV <= 0 || H != 2 * KV) return false;
+    const Knobs &kn = knobs();
+    const int cus = num_cus_attn(), nq = (Sq + QB - 1) / QB, unit_tiles = (Sk + KT - 1) / KT;
+    if (kn.attn_small && (int64_t)((Sq + 31) / 32) * H * B <= cus + cus / 2) return false;   // attn_small_kernel
+    if (kn.attn_pw & (Sk == Sq ? 1 : 4)) return false;                                       // attn_pw_kernel
+    const bool short_split = nq * KV * B * 2 <= cus && unit_tiles >= 4;
+    if (short_split) return !have_ws;                       // every unit split over KV ranges
+    if (unit_tiles < 24 && nq * KV * B > cus) return true;  // one head per workgroup, whole units
+    const int units = nq * KV * B, tail = units % cus;
+    if (have_ws && unit_tiles >= 24 && units > cus && tail > 0) return false;   // tail split / stream-K
+    return true;
+}
+
+int attention_fwd_units(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int Sq,
+                        int Sk, float scale, int64_t o_ld, hipStream_t s) {
+    if (B <= 0 || Sq <= 0 || Sk <= 0 || KV <= 0 || H != 2 * KV || o_ld % 8)
+        return fail(-1, "attention_fwd_units: bad heads/lengths");
+    const int nq = (Sq + QB - 1) / QB, units = nq * KV * B;
+    SplitArgs sp{nq, units, 1, nullptr, nullptr};
+    attn_fwd_kernel<2><<<units, 512, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, -1, scale * 1.4426950408889634f, o_ld, sp,
+                                              nullptr);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV,

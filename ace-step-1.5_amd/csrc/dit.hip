@@ -870,17 +870,33 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
             cq.M = Mq; cq.N = qd; cq.K = D; cq.epi = EPI_HEADPOST;
             cq.hp.B = Bq; cq.hp.S = S; cq.hp.nq = H; cq.hp.qw = ly.cqn; cq.hp.q = h->Qh; cq.hp.S_dst = S;
             cq.hp.eps = eps;
-            RUN(hgemm(h, cq, s));
+            cq.ws = h->gemm_ws;
+            cq.ws_bytes = h->gemm_ws ? GEMM_WS_BYTES : 0;
             AttnProbsSel sel;
-            if (cap && capture_layer(cap, l, sel)) {
-                RUN(attention_probs(h->Qh, h->Kc + l * cper, Bq, H, KV, S, Le, sel, cap->k0, cap->k1, scale, cap->out,
-                                    s));
-                if (cap->stop_after_last && l == capture_last_layer(cap)) return 0;
+            const bool captured = cap && capture_layer(cap, l, sel);
+            // One launch for the projection and the attention (cross_q_attn_kernel: the Q tile stays
+            // in LDS) where the projection runs on the half-chip four-wave tile, the attention as
+            // whole units on attn_fwd_kernel and every 192-row tile lies in one batch element; a
+            // captured layer needs Q in global memory.  Bit-identical to the two launches
+            // (ACEHIP_CROSS_FUSE=0), which then take exactly those two kernels.
+            const bool fusable = cross_fuse_shape(cq, KV, Le) && cross_fuse_planned(cq) &&
+                                 attention_whole_units(Bq, H, KV, S, Le, h->attn_ws != nullptr);
+            if (fusable && knobs().cross_fuse && !captured) {
+                RUN(timed(h, 6, s, [&] {
+                    return cross_q_attention(cq, h->Kc + l * cper, h->Vc + l * cper, h->AO, KV, Le, scale, qd, s);
+                }));
+            } else {
+                RUN(fusable ? gemm_variant(cq, 13, s) : gemm(cq, s));
+                if (captured) {
+                    RUN(attention_probs(h->Qh, h->Kc + l * cper, Bq, H, KV, S, Le, sel, cap->k0, cap->k1, scale,
+                                        cap->out, s));
+                    if (cap->stop_after_last && l == capture_last_layer(cap)) return 0;
+                }
+                RUN(timed(h, 6, s, [&] {
+                    return attention(h->Qh, h->Kc + l * cper, h->Vc + l * cper, h->AO, Bq, H, KV, S, Le, -1, scale, qd,
+                                     h->attn_ws, s);
+                }));
             }
-            RUN(timed(h, 6, s, [&] {
-                return attention(h->Qh, h->Kc + l * cper, h->Vc + l * cper, h->AO, Bq, H, KV, S, Le, -1, scale, qd,
-                                 h->attn_ws, s);
-            }));
             GemmArgs co{};
             co.A = h->AO; co.lda = qd; co.W = ly.wco; co.ldw = qd; co.C = h->X; co.ldc = D;
             co.M = Mq; co.N = D; co.K = qd; co.epi = EPI_RES; co.res = h->X; co.ldr = D;
@@ -1122,6 +1138,63 @@ int acehip_gemm_headpost_bf16(const void *A, int lda, const void *W, int K, int 
     g.ws = abi_gemm_ws();
     g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
     return gemm(g, (hipStream_t)stream);
+}
+
+// lazily allocated Q scratch of acehip_cross_attn_bf16's two-launch path (one per device, grown on demand)
+static bf16_t *abi_cross_q(size_t bytes) {
+    static std::map<int, std::pair<void *, size_t>> by_dev;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    std::lock_guard<std::mutex> lk(g_abi_ws_mu);
+    auto &e = by_dev[dev];
+    if (e.second < bytes) {
+        if (e.first) {
+            (void)hipDeviceSynchronize();
+            (void)hipFree(e.first);
+        }
+        e = {nullptr, 0};
+        if (hipMalloc(&e.first, bytes) != hipSuccess) return nullptr;
+        e.second = bytes;
+    }
+    return (bf16_t *)e.first;
+}
+
+int acehip_cross_attn_bf16(const void *xn, const void *wq, const void *qnw, const void *k, const void *v, void *ao,
+                           int B, int S, int H, int KV, int Lenc, int D, float eps, float scale, int force,
+                           int *path, void *stream) {
+    if (!xn || !wq || !qnw || !k || !v || !ao || !path) return fail(ACEHIP_E_ARG, "cross_attn: null argument");
+    if (B <= 0 || S <= 0 || H <= 0 || KV <= 0 || Lenc <= 0 || D <= 0 || D % 64 || H % 2 || (int64_t)B * S > INT32_MAX)
+        return fail(ACEHIP_E_ARG, "cross_attn: shape");
+    if (force < -1 || force > 1) return fail(ACEHIP_E_ARG, "cross_attn: force must be -1, 0 or 1");
+    *path = -1;
+    hipStream_t s = (hipStream_t)stream;
+    GemmArgs cq{};
+    cq.A = (const bf16_t *)xn; cq.lda = D; cq.W = (const bf16_t *)wq; cq.ldw = D;
+    cq.M = B * S; cq.N = H * 128; cq.K = D; cq.epi = EPI_HEADPOST;
+    cq.hp.B = B; cq.hp.S = S; cq.hp.nq = H; cq.hp.qw = (const bf16_t *)qnw; cq.hp.S_dst = S; cq.hp.eps = eps;
+    cq.ws = abi_gemm_ws();
+    cq.ws_bytes = cq.ws ? GEMM_WS_BYTES : 0;
+    const int64_t qd = (int64_t)H * 128;
+    const bool shape = cross_fuse_shape(cq, KV, Lenc);
+    const bool planned = shape && cross_fuse_planned(cq) && attention_whole_units(B, H, KV, S, Lenc, true);
+    // force = 1: fused wherever the kernel can run the shape; 0: the two launches it fuses
+    // (variant 13 + whole units on attn_fwd_kernel); −1: forward_body's own choice
+    const bool fused = shape && (force == 1 || (force < 0 && planned && knobs().cross_fuse));
+    if (fused) {
+        *path = 1;
+        return cross_q_attention(cq, (const bf16_t *)k, (const bf16_t *)v, (bf16_t *)ao, KV, Lenc, scale, qd, s);
+    }
+    *path = 0;
+    cq.hp.q = abi_cross_q((size_t)B * S * qd * sizeof(bf16_t));
+    if (!cq.hp.q) return fail(ACEHIP_E_OOM, "cross_attn: Q scratch");
+    if (force == 0 || planned) {
+        if (H != 2 * KV) return fail(ACEHIP_E_ARG, "cross_attn: the forced two-launch path needs H = 2 KV");
+        if (int rc = gemm_variant(cq, 13, s)) return rc;
+        return attention_fwd_units(cq.hp.q, (const bf16_t *)k, (const bf16_t *)v, (bf16_t *)ao, B, H, KV, S, Lenc,
+                                   scale, qd, s);
+    }
+    if (int rc = gemm(cq, s)) return rc;
+    return acehip_attention_bf16(cq.hp.q, k, v, ao, B, H, KV, S, Lenc, -1, scale, stream);
 }
 
 int acehip_attention_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV,

@@ -28,6 +28,7 @@
 
 #include <type_traits>
 
+#include "attn_tile.h"
 #include "kernels.h"
 #include "headpost.h"
 #include "pp_addr.h"
@@ -559,6 +560,138 @@ __device__ __forceinline__ void headpost_epilogue(const GemmArgs &a, char *lds, 
     }
 }
 
+// the attention half's arguments of the fused cross-Q projection + cross-attention kernel
+struct XAttnArgs {
+    const bf16_t *k, *v;   // [B][KV][Sk][128]
+    bf16_t *o;             // token-major [B·S][o_ld], head h at column h·128
+    int KV, Sk;
+    float sl2;             // scale · log2(e)
+    int64_t o_ld;
+};
+
+// Epilogue of the fused cross-Q projection + cross-attention tile (w4_body XATT): BM = 192 rows
+// × one q head, six waves.  The operand ring is dead after the K loop; LDS becomes
+//   [0, QIMG)               the bf16 Q tile [192][PITCH] — the head-post staging tile, transformed
+//                           in place (q RMSNorm, no RoPE: headpost_rows' MODE 1 arithmetic)
+//   [QIMG, QIMG + 4 tiles)  the attention's K/V ring, K slots 0, 1 then V slots 0, 1 (attn_tile.h)
+// Wave w owns rows [32w, 32w + 32) from the transform on: it normalises them, reads them back as
+// its Q fragments and runs attn_fwd_kernel's per-wave tile body over KV tiles 0 … ⌈Sk / 64⌉ − 1,
+// so nothing but the two block barriers around store_acc orders the waves before the tile loop.
+// The transform's LDS accesses are inline asm (explicit lgkmcnt waits): the first K/V tile's
+// LDS-DMA is already in flight, and the compiler would drain it (vmcnt(0)) before any LDS access
+// of its own.  Per KV tile: one barrier, every wave — rows past M included — reaches it.
+// The tile lies inside one batch element (the dispatch guarantees it), rows ≥ M are not stored.
+template <int BM, int LDS_BYTES, typename StoreAcc>
+__device__ __forceinline__ void xattn_epilogue(const GemmArgs &a, const XAttnArgs &xa, char *lds, int m0, int n0,
+                                               int wave, int lane, bool mfma_wave, StoreAcc store_acc) {
+    constexpr int PITCH = 136;                       // 16-B aligned rows (headpost_epilogue's pitch)
+    constexpr int QIMG = BM * PITCH * 2;             // bytes of the Q tile
+    constexpr int NBUF = 2;
+    static_assert(BM == 6 * 32, "six waves × 32 query rows");
+    static_assert(QIMG % 1024 == 0 && QIMG + 2 * NBUF * KV_TILE <= LDS_BYTES, "Q tile + K/V ring must fit the operand ring");
+    const HeadPostArgs &h = a.hp;
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int r = lane & 31, hh = lane >> 5;
+    const int sub = lane >> 4, li = lane & 15, d = li * 8;
+    const int head = n0 >> 7, kvh = head / (h.nq / xa.KV), b = m0 / h.S;
+    const int Sk = xa.Sk;
+    const float sl2 = xa.sl2;
+    const bf16_t *kp = xa.k + ((int64_t)b * xa.KV + kvh) * (int64_t)Sk * 128;
+    const bf16_t *vp = xa.v + ((int64_t)b * xa.KV + kvh) * (int64_t)Sk * 128;
+    const int ntiles = (Sk + KT - 1) / KT;
+    float w[8];
+    unpack8(*(const uint4 *)(h.qw + d), w);
+    char *const ring = lds + QIMG;
+
+    __syncthreads();                                 // every wave is past the operand ring
+    if (mfma_wave) store_acc((bf16_t *)lds, PITCH);
+    __syncthreads();
+    asm volatile("" ::: "memory");
+
+    // LDS-DMA staging of one K/V tile, attn_fwd_kernel's image (32 one-KiB pieces; waves 0 and 1
+    // issue six, the others five): piece c covers image rows 4c..4c+3 of K (c < 16) or V, lane L
+    // fetches the logical chunk that kvoff() places in the 16-B slot (row 4c + L/16, chunk L%16).
+    // Rows past Sk are clamped to a real row: those keys are masked (K) or meet P = 0 (V).
+    auto stage_piece = [&](int kv0, int buf, int c) {
+        const int isv = c >> 4, row = (c & 15) * 4 + (lane >> 4), pc = lane & 15;
+        const int ch = pc ^ (((row & 3) << 2) | ((row >> 2) & 3));
+        const int key = min(kv0 + row, Sk - 1);
+        glds16((isv ? vp : kp) + (int64_t)key * 128 + ch * 8, ring + (isv * NBUF + buf) * KV_TILE + (c & 15) * 1024);
+    };
+    auto stage_tile = [&](int kv0, int buf) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) stage_piece(kv0, buf, wv + 6 * i);   // pieces 0 .. 29
+        if (wv < 2) stage_piece(kv0, buf, 30 + wv);
+    };
+    stage_tile(0, 0);
+
+    // q RMSNorm of the wave's 32 rows, four rows (one per 16-lane group) per step, in place
+    {
+        const float none[8] = {};
+        bf16x8 raw[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) raw[it] = ds_read_b128(lds + ((wv * 32 + it * 4 + sub) * PITCH + d) * 2);
+        lgkm_wait8(raw);
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            float x[8];
+            unpack8(__builtin_bit_cast(uint4, raw[it]), x);
+            head_norm_rope_t<true, false>(x, li, w, none, none, h.eps);
+            const uint4 pk = pack8(x);
+            const u32x4 out = {pk.x, pk.y, pk.z, pk.w};
+            const uint32_t dst = lds_addr(lds + ((wv * 32 + it * 4 + sub) * PITCH + d) * 2);
+            asm volatile("ds_write_b128 %0, %1" ::"v"(dst), "v"(out) : "memory");
+        }
+    }
+    // Q fragments (B operand of Sᵀ = K·Qᵀ): lane (r, hh) holds Q[32w + r][16s + 8hh .. +8]; the
+    // reads follow the wave's own writes in its LDS queue
+    bf16x8 qf[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) qf[s] = ds_read_b128(lds + ((wv * 32 + r) * PITCH + 16 * s + 8 * hh) * 2);
+    lgkm_wait8(qf);
+
+    float m = NEG, l = 0.f;
+    f32x16 oacc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) oacc[i][j] = 0.f;
+    const uint32_t ring_base = lds_addr(ring);
+    uint32_t koff[8], voff[4][2];
+    attn_lane_offsets(ring_base, ring_base + NBUF * KV_TILE, lane, koff, voff);
+
+    // end-of-tile wait (counted: the one tile in flight) + the tile's one barrier, as in
+    // attn_fwd_kernel: own DMAs of the next tile landed, own LDS reads retired
+    auto tile_barrier = [&] {
+        wait_vm_lgkm0<0>();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    auto tile = [&](int it, auto SLOTC) {
+        constexpr int SLOT = decltype(SLOTC)::value;
+        constexpr int KB = SLOT * KV_TILE, VB = SLOT * KV_TILE;
+        const int kv0 = it * KT;
+        // refill: tile it+1 into the slot of tile it−1, read by nobody now
+        if (it + 1 < ntiles) stage_tile(kv0 + KT, (SLOT + 1) % NBUF);
+        attn_wave_tile<KB, VB>(qf, koff, voff, oacc, m, l, sl2, kv0 + KT <= Sk, [&](int t, int j, float sc) {
+            const int kj = kv0 + 32 * t + (j & 3) + 8 * (j >> 2) + 4 * hh;
+            return kj < Sk ? sc : NEG;
+        });
+        tile_barrier();
+    };
+    tile_barrier();
+    int it = 0;
+    for (; it + 1 < ntiles; it += 2) {
+        tile(it, IC<0>{});
+        tile(it + 1, IC<1>{});
+    }
+    if (it < ntiles) tile(it, IC<0>{});
+
+    const int row = m0 + wv * 32 + r;                // token b·S + s: AO is token-major
+    if (row < a.M)                                   // both lanes of a row pair (lane, lane ^ 32) agree
+        attn_wave_store_o(oacc, l, xa.o + (int64_t)row * xa.o_ld + head * 128, hh);
+}
+
 // ---------------------------------------------------------------------------
 // Ping-pong variant: BM×256 tile, 8 waves as 2 groups (wr = 0/1, A rows
 // [wr·BM/2, +BM/2)) × 4 (64 columns each).  The groups run one barrier apart,
@@ -975,16 +1108,28 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_split_kernel(GemmArgs a, GemmA
 // MFMA waves carry no DMA in their instruction stream (one wave per SIMD pays ≈ 60-185 cycles
 // per piece there); a helper waits for tile kt+1 before barrier kt and refills tile kt's buffer
 // after it, the same ordering as the MFMA waves' own refills
-template <int BM, int BN, int EPI, int NH = 0>
-__global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
+//
+// XATT (the fused cross-attention kernel below; BM = 192, BN = 128, NH = 2, head-post epilogue): the
+// tile is the cross-Q projection of 192 rows × one head.  After the K loop the bf16 Q rows stay
+// in LDS and all six waves — the helper waves included, 32 rows each — run the cross-attention
+// of those rows over the layer's cached K/V (attn_tile.h, attn_fwd_kernel's per-wave body) and
+// write AO (xattn_epilogue above).
+
+// ring depth: 3 tile buffers when they fit (a refill's DMA then has two K-tiles of lead,
+// enough for HBM-cold weights), else 2 (one K-tile of lead)
+template <int BM, int BN>
+constexpr int w4_stages() { return 3 * (BM + BN) * 128 <= 160 * 1024 ? 3 : 2; }
+template <int BM, int BN>
+constexpr int w4_lds_bytes() { return w4_stages<BM, BN>() * (BM + BN) * 128; }
+
+template <int BM, int BN, int EPI, int NH, bool XATT>
+__device__ __forceinline__ void w4_body(const GemmArgs &a, char *lds, const XAttnArgs &xa) {
     constexpr int TM = BM / 2, TN = BN / 2, SM = TM / 16, SN = TN / 16;
     constexpr int ROWS = BM + BN, STAGE = ROWS * 128;
-    // ring depth: 3 tile buffers when they fit (a refill's DMA then has two K-tiles of lead,
-    // enough for HBM-cold weights), else 2 (one K-tile of lead)
-    constexpr int NS = 3 * STAGE <= 160 * 1024 ? 3 : 2;
+    constexpr int NS = w4_stages<BM, BN>();
     constexpr int PW = ROWS / 32;                              // glds per wave per K-tile
     static_assert(ROWS % 32 == 0, "staging must split evenly over 4 waves");
-    __shared__ __attribute__((aligned(16))) char lds[NS * STAGE];
+    static_assert(!XATT || (BM == 192 && BN == 128 && NH == 2 && EPI == EPI_HEADPOST), "fused cross-attention tile");
 
     GSTAMP(0);
     GSTAMP_REAL(4);
@@ -1001,6 +1146,7 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
     const int m0 = tm * BM, n0 = tn * BN;
     const int nk = a.K / BK;
 
+    bool mfma_wave = true;   // false: a helper wave of the fused kernel, past its DMA loop
     if constexpr (NH > 0) {
         if (__builtin_amdgcn_readfirstlane(wave) >= 4) {
             constexpr int PPH = 4 * PW / NH;                        // pieces per helper per K-tile
@@ -1028,14 +1174,21 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
                 fill(kt % NS, min(kt + NS, nk - 1) * BK);
             }
             wait_vm<0>();
-            if constexpr (EPI == EPI_HEADPOST) {   // the head-post epilogue's two block barriers
-                __syncthreads();
-                __syncthreads();
+            if constexpr (XATT) {
+                mfma_wave = false;                 // joins the fused epilogue below
+            } else {
+                if constexpr (EPI == EPI_HEADPOST) {   // the head-post epilogue's two block barriers
+                    __syncthreads();
+                    __syncthreads();
+                }
+                return;
             }
-            return;
         }
     }
 
+    const int fr = lane & 15, fc = lane >> 4;
+    f32x4 acc[SM][SN];
+    if (mfma_wave) {
     // staging: wave issues image rows [8q, 8q+8) for q = wave + 4i (swizzle on the source)
     const bf16_t *src[PW];
 #pragma unroll
@@ -1046,13 +1199,11 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
         else src[i] = a.W + (int64_t)(n0 + r - BM) * a.ldw + c * 8;
     }
     auto stage1 = [&](int buf, int k0, int i) { glds16(src[i] + k0, lds + buf * STAGE + (wave + 4 * i) * 1024); };
-    f32x4 acc[SM][SN];
 #pragma unroll
     for (int i = 0; i < SM; ++i)
 #pragma unroll
         for (int j = 0; j < SN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int fr = lane & 15, fc = lane >> 4;
     const int xrow = wm * TM + fr, wrow = BM + wn * TN + fr;
     bf16x8 x0[SM], w0[SN], x1[SM], w1[SN];
     auto rd = [&](const char *b, int ks, bf16x8 (&xf)[SM], bf16x8 (&wf)[SN]) {
@@ -1072,7 +1223,12 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
         for (int i = 0; i < SM; ++i)
 #pragma unroll
             for (int j = 0; j < SN; ++j) {
-                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(wf[j]), "v"(xf[i]));
+                // (XATT: in arch VGPRs — the attention half needs nearly all 256 registers of the
+                // wave as arch VGPRs, and the AGPR / VGPR boundary is one per kernel)
+                if constexpr (XATT)
+                    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(wf[j]), "v"(xf[i]));
+                else
+                    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(wf[j]), "v"(xf[i]));
                 hook(i * SN + j);
             }
     };
@@ -1137,16 +1293,22 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
     // before their accumulators are read
     GSTAMP(2);
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-    if constexpr (EPI == EPI_HEADPOST) {
-        headpost_epilogue<BM, 4, sizeof(lds), BN / 128>(a, lds, m0, n0, wave, lane, [&](bf16_t *st, int pitch) {
+    }   // mfma_wave
+    // the wave's accumulators as bf16 into the LDS tile st[BM][pitch] (head-post staging)
+    auto store_acc = [&](bf16_t *st, int pitch) {
 #pragma unroll
-            for (int i = 0; i < SM; ++i)
+        for (int i = 0; i < SM; ++i)
 #pragma unroll
-                for (int j = 0; j < SN; ++j) {
-                    float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                    *(uint2 *)(st + (wm * TM + i * 16 + fr) * pitch + wn * TN + j * 16 + fc * 4) = pack4(o);
-                }
-        });
+            for (int j = 0; j < SN; ++j) {
+                float o[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+                *(uint2 *)(st + (wm * TM + i * 16 + fr) * pitch + wn * TN + j * 16 + fc * 4) = pack4(o);
+            }
+    };
+    (void)store_acc;
+    if constexpr (XATT) {
+        xattn_epilogue<BM, NS * STAGE>(a, xa, lds, m0, n0, wave, lane, mfma_wave, store_acc);
+    } else if constexpr (EPI == EPI_HEADPOST) {
+        headpost_epilogue<BM, 4, NS * STAGE, BN / 128>(a, lds, m0, n0, wave, lane, store_acc);
     } else {
         epilogue_tile<SM, SN, EPI>(a, acc, m0 + wm * TM, n0 + wn * TN, fr, fc);
     }
@@ -1155,6 +1317,20 @@ __global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
 #endif
     GSTAMP(3);
     GSTAMP_REAL(5);
+}
+
+template <int BM, int BN, int EPI, int NH = 0>
+__global__ __launch_bounds__(256 + 64 * NH, 1) void gemm_w4_kernel(GemmArgs a) {
+    __shared__ __attribute__((aligned(16))) char lds[w4_lds_bytes<BM, BN>()];
+    w4_body<BM, BN, EPI, NH, false>(a, lds, XAttnArgs{});
+}
+
+// The fused cross-Q projection + cross-attention of the DiT's conditional rows: gemm_w4_kernel<192,
+// 128, head-post, 2 helpers>'s tile (one 192-row tile × one head per workgroup), whose Q rows go to
+// LDS and whose six waves then attend over the cached K/V of that head's KV head (w4_body XATT)
+__global__ __launch_bounds__(384, 1) void cross_q_attn_kernel(GemmArgs a, XAttnArgs xa) {
+    __shared__ __attribute__((aligned(16))) char lds[w4_lds_bytes<192, 128>()];
+    w4_body<192, 128, EPI_HEADPOST, 2, true>(a, lds, xa);
 }
 
 template <int BM, int BN = 256, int NH = 0>
@@ -1573,6 +1749,39 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
         if (tiles > plan_cus() && tiles < (1ll << 30)) return launch_pp_persist(a, a, (int)tiles, 0, s);
     }
     return gemm_variant(a, v, s);
+}
+
+// ---------------------------------------------------------------------------
+// Fused cross-Q projection + cross-attention (cross_q_attn_kernel).  cq is the cross-Q head-post
+// GEMM as forward_body builds it (q heads only, no RoPE; cq.hp.q is not written).
+// cross_fuse_shape: what the kernel itself needs — one q head per 128 columns, two q heads per KV
+// head, and every 192-row tile inside one batch element.
+bool cross_fuse_shape(const GemmArgs &cq, int KV, int Sk) {
+    const HeadPostArgs &h = cq.hp;
+    return cq.epi == EPI_HEADPOST && cq.M > 0 && cq.K > 0 && cq.K % BK == 0 && cq.N == h.nq * 128 && h.nk == 0 &&
+           h.nv == 0 && !h.cos && !h.sin && h.qw && h.m_off == 0 && h.S > 0 && (int64_t)h.B * h.S == cq.M &&
+           KV > 0 && h.nq == 2 * KV && Sk > 0 && (h.B == 1 || h.S % 192 == 0) && (cq.lda | cq.ldw) % 8 == 0;
+}
+// cross_fuse_planned: gemm() runs cq on the half-chip four-wave tile with its helper waves
+// (variant 13: one round of 192 × 128 tiles on at least three quarters of the planned CUs, and
+// not the small-M split-K path); the CU count is the planner's (ACEHIP_GEMM_CUS in tests)
+bool cross_fuse_planned(const GemmArgs &cq) {
+    if (!knobs().gemm_helpers || cq.N % 256) return false;
+    const int cus = plan_cus();
+    const int64_t t = (int64_t)((cq.M + 191) / 192) * (cq.N / 128);
+    const int64_t t128 = (int64_t)((cq.M + 127) / 128) * (cq.N / 128);
+    if (cq.ws && t128 * 2 <= cus && cq.K / BK >= 8) return false;   // split-K
+    return t <= cus && t * 4 >= (int64_t)cus * 3;
+}
+int cross_q_attention(const GemmArgs &cq, const bf16_t *k, const bf16_t *v, bf16_t *o, int KV, int Sk, float scale,
+                      int64_t o_ld, hipStream_t s) {
+    if (!cross_fuse_shape(cq, KV, Sk)) return fail(-1, "cross_q_attention: shape outside the fused kernel's");
+    if (!k || !v || !o || o_ld % 8 || o_ld < cq.N) return fail(-1, "cross_q_attention: K / V / O");
+    XAttnArgs xa{k, v, o, KV, Sk, scale * 1.4426950408889634f, o_ld};
+    const int tiles = ((cq.M + 191) / 192) * (cq.N / 128);
+    cross_q_attn_kernel<<<tiles, 384, 0, s>>>(cq, xa);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 }  // namespace acehip

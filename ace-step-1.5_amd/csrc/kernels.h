@@ -32,6 +32,7 @@ struct Knobs {
     int convp = 3;            // ACEHIP_CONVP: 0 none, 1 all, 2 k = 1 convs on convp_kernel, 3 k = 1 convs with N % 256 == 0 on the ping-pong GEMM (the rest on conv_gemm_kernel)
     int ru7 = 2;              // ACEHIP_RU7: C = 128 residual unit — 2 ru8_kernel (256-row tiles), 1 ru7_kernel, 0 conv7
     int vae_snake_in = 1;     // ACEHIP_VAE_SNAKE_IN: C = 128 decoder blocks without x_s tensors (ru8 SIN)
+    int cross_fuse = 1;       // ACEHIP_CROSS_FUSE: the conditional rows' cross-Q projection and cross-attention as one launch (cross_q_attn_kernel) where the shape allows, 0: two launches
     int kv_group_kib = 262144; // ACEHIP_KV_GROUP_KIB: cross-K/V scratch bound at dit_create (tests force small groups)
     unsigned gen = 0;
 };
@@ -104,6 +105,15 @@ struct RowAdd;
 // consumer rmsnorm_mod applies it, one launch fewer); defer->part stays null otherwise
 int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer = nullptr);
 int gemm_variant(const GemmArgs &a, int variant, hipStream_t s);   // tuning / tests
+// Cross-Q projection + cross-attention in one launch (gemm.hip cross_q_attn_kernel): cq = the
+// cross-Q head-post GEMM (q heads only, no RoPE; its hp.q is not written), k / v [B][KV][Sk][128]
+// → o token-major [B·S][o_ld] — bit-identical to gemm_variant(cq, 13) + attention() on
+// attn_fwd_kernel.  cross_fuse_shape: the shapes the kernel runs; cross_fuse_planned: gemm()
+// would run cq on variant 13 with helper waves (planner CU count).
+bool cross_fuse_shape(const GemmArgs &cq, int KV, int Sk);
+bool cross_fuse_planned(const GemmArgs &cq);
+int cross_q_attention(const GemmArgs &cq, const bf16_t *k, const bf16_t *v, bf16_t *o, int KV, int Sk, float scale,
+                      int64_t o_ld, hipStream_t s);
 // VAE convolutions (k = 7 dilated, ConvTranspose phases) on the two-phase ping-pong tile
 // (EPI_CONV; the caller provides the input's zero halo rows)
 int gemm_conv(const GemmArgs &a, hipStream_t s);
@@ -178,6 +188,12 @@ int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int 
               int Sq, int Sk, int window, float scale, int64_t o_ld, void *ws, hipStream_t s,
               const uint8_t *kmask = nullptr);
 size_t attention_ws_bytes();
+// Whether attention() runs this unmasked, unwindowed shape as whole units on attn_fwd_kernel (no
+// attn_small_kernel, attn_pw_kernel, KV split or stream-K): the fused cross kernel's per-wave
+// arithmetic is that path's.  attention_fwd_units launches exactly that, whatever the CU count.
+bool attention_whole_units(int B, int H, int KV, int Sq, int Sk, bool have_ws);
+int attention_fwd_units(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int Sq,
+                        int Sk, float scale, int64_t o_ld, hipStream_t s);
 
 // Normalised softmax rows of selected heads (attn_probs.hip; fp32 twin in f32.hip):
 //   out[slot[i]][b][j − k0][s] = softmax_j(scale · q[b, head[i], s, :] · k[b, head[i] / (H/KV), j, :])

@@ -44,6 +44,7 @@ Knobs read_env() {
     k.ru7 = env_int("ACEHIP_RU7", 2);
     k.kv_group_kib = env_int("ACEHIP_KV_GROUP_KIB", 262144);
     k.vae_snake_in = env_int("ACEHIP_VAE_SNAKE_IN", 1);
+    k.cross_fuse = env_int("ACEHIP_CROSS_FUSE", 1);
     if (k.kv_group_kib <= 0) k.kv_group_kib = 262144;
     return k;
 }

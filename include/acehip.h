@@ -532,6 +532,18 @@ int acehip_gemm_headpost_bf16(const void *A, int lda, const void *W, int K, int 
                               int nk, int nv, const void *qw, const void *kw, const void *cos,
                               const void *sin, float eps, void *q, void *k, void *v, void *stream);
 
+/* Cross-attention of the DiT's conditional rows from the normed hidden states (tests, tools):
+ * Q = q_norm(xn · wqᵀ) per head (no RoPE), AO = softmax(scale · Q Kᵀ) V over the cached k / v
+ * [B,KV,Lenc,128]; xn [B·S,D], wq [H·128,D], qnw [128], ao token-major [B·S,H·128].
+ * force = 1: the fused projection + attention launch wherever that kernel can run the shape
+ * (H = 2·KV, B = 1 or S % 192 = 0), whatever the CU count; 0: the two launches it fuses (the
+ * four-wave projection tile, then whole units on the forward attention kernel); −1: the DiT
+ * forward's own choice (ACEHIP_CROSS_FUSE and the CU-count conditions).
+ * *path = 1 if the fused launch ran, 0 if two launches did. */
+int acehip_cross_attn_bf16(const void *xn, const void *wq, const void *qnw, const void *k, const void *v, void *ao,
+                           int B, int S, int H, int KV, int Lenc, int D, float eps, float scale, int force,
+                           int *path, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
