@@ -17,10 +17,19 @@
 // fused in the same epilogue.  The residual may alias the raw output (each
 // element is read and written by the same lane).
 //
-// Tile 128×128×64, 4 waves (2×2) of v_mfma_f32_16x16x32_bf16; both operands
-// are staged one tile ahead — W by global_load_lds into a double buffer, the
-// A (im2col) tile through registers (its global loads are in flight during
-// the MFMAs of the current tile), XOR-swizzled for conflict-free ds_read_b128.
+//
+// Which kernel runs what (conv_gemm() and resunit128() at the end of the file):
+//   * gemm_conv — the two-phase ping-pong GEMM tile of gemm.hip (EPI_CONV): the C ≥ 256 k = 7
+//     convs, every ConvTranspose and the C ≥ 256 k = 1 residual tails, all on padded
+//     activation buffers;
+//   * ru8_kernel<RAW, SIN> — every C = 128 residual unit, whole (k7 → Snake → k1 → +x → Snake);
+//     ru7_kernel is its bit-exact oracle (ACEHIP_RU7=1);
+//   * conv7_kernel — the k = 7 convs whose input is not a padded activation buffer (the
+//     decoder's first conv, 64 → 2048; every k = 7 conv with ACEHIP_CONV7=1);
+//   * conv_gemm_kernel — everything else: the encoder's strided convs and its k = 3 output
+//     conv (and the A/B arms ACEHIP_CONVT=0, ACEHIP_CONVP=0);
+//   * conv_out / conv_in and the small kernels: the 2-channel audio ends, layout and weight
+//     preparation.
 #include "kernels.h"
 #include "conv.h"
 #include <algorithm>
@@ -48,8 +57,12 @@ __device__ __forceinline__ void snake8(const float (&x)[8], const float *sa, con
     snake_n<8>(x, av, bv, y);
 }
 
-// Both operands by global_load_lds into a 2-stage ring: [A im2col rows | W rows],
-// 128-B rows, XOR-swizzled on the source address (as gemm.hip).
+// The general implicit-GEMM conv (any taps / stride / dilation / phases, optional residual,
+// raw and / or snaked output).  Tile 128×128×64, 4 waves (2×2, 64×64 wave tiles) of
+// v_mfma_f32_16x16x32_bf16, two blocks per CU; one block per (M-tile, N-tile), gridDim.y = the
+// ConvTranspose phases.  Both operands by global_load_lds into a 2-stage ring, one K-tile
+// ahead: [A im2col rows | W rows], 128-B rows, XOR-swizzled on the source address (as gemm.hip)
+// for conflict-free ds_read_b128; vmcnt(0) and one barrier per K-tile.
 struct ConvTile {
     static constexpr int BM = 128, BN = 128, ROWS = BM + BN, STAGE = ROWS * 128;
 };
@@ -154,403 +167,56 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ConvArgs a) {
     }
 }
 
-// ---------------------------------------------------------------------------
-// Persistent implicit-GEMM conv for the ConvTranspose phases, the k = 1 convs at C ≥ 256
-// and the encoder's strided convs.  conv_gemm_kernel stages one K-tile ahead on a 2-slot
-// ring, waits vmcnt(0) every K-tile and starts every tile with the operand latency
-// exposed; with 4–32 K-tiles per tile those launches ran at ≈ 40 % of the HBM roof.
-// Here one block per CU (8 waves, 64×32 wave tiles) walks a contiguous range of work
-// items (M-tile, N-tile, phase; phase fastest, then N, so consecutive items share the A
-// panel in L2 — phases as the slowest index sent every ConvTranspose input through HBM
-// once per phase)
-// and the K-tiles of consecutive items form ONE stream through an NS-stage ring
-// (NS = 4, or 3 with a residual): NS − 1 stages are in flight, so the next item's
-// operands land during the current item's epilogue.
-// All loads are LDS-DMA by inline asm with explicit counted waits (hipcc, seeing no
-// vector loads in the loop, inserts no waits of its own — with the builtin DMA it placed
-// vmcnt(0) at every loop merge): the operand stages, the item's residual tile (issued at
-// its first K-step into a swizzled 32 KiB image) and, once per block, the bias / Snake
-// parameters of all N columns.  vmcnt per wave at K-step g (stage g issued at g − NS + 1):
-// younger are the ≤ NS − 2 newer stages, the residual pieces if the item began at a step
-// after stage g was issued, and the previous epilogue's stores if they followed it
-// (partial tiles, whose store count varies, are left out: a safe over-wait).
-namespace cp {
-constexpr int BM = 128, BN = 128, STAGE = (BM + BN) * 128, NW = 8;
-constexpr int PW = (BM + BN) / 8 / NW;                    // operand pieces per wave per stage
-constexpr int RW = BM * 256 / 1024 / NW;                  // residual pieces per wave per item
-constexpr int WM = 2, WN = 4, TM = BM / WM, TN = BN / WN, SM = TM / 16, SN = TN / 16;   // 64×32
-constexpr int MAXN = 1024;                                // parameter image: N ≤ 1024 columns
-constexpr int PAR = MAXN * 10;                            // bias bf16 | sa f32 | sib f32
-}  // namespace cp
-
-template <bool RES, bool RAW, bool SN>
-__global__ __launch_bounds__(512, 1) void convp_kernel(ConvArgs a, int64_t nitems, int phases) {
-    constexpr int CBM = cp::BM, CBN = cp::BN, STG = cp::STAGE, PW = cp::PW, RW = RES ? cp::RW : 0;
-    constexpr int NS = RES ? 3 : 4;
-    constexpr int SM = cp::SM, SNT = cp::SN, TM = cp::TM, TN = cp::TN;
-    constexpr int KST = ((RAW ? 1 : 0) + (SN ? 1 : 0)) * SM;   // epilogue stores per wave per item
-    constexpr int RESB = RES ? CBM * 256 : 0;
-    __shared__ __attribute__((aligned(16))) char lds[cp::PAR + NS * STG + RESB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / cp::WN, wn = wave % cp::WN;
-    const int fr = lane & 15, fc = lane >> 4;
-    const bool odd = fc & 1;
-    const int64_t i0 = nitems * blockIdx.x / gridDim.x, i1 = nitems * (blockIdx.x + 1) / gridDim.x;
-    if (i0 >= i1) return;
-    const int K = a.taps * a.Cin, nk = K / BK;
-    const int64_t G = (i1 - i0) * nk;
-    const int tilesN = a.N / CBN;
-    // parameters of all N columns → LDS (plain loads, retired before the first DMA)
-    bf16_t *pbias = (bf16_t *)lds;
-    float *psa = (float *)(lds + cp::MAXN * 2), *psib = psa + cp::MAXN;
-    for (int c = tid; c < a.N; c += 512) {
-        pbias[c] = a.bias ? a.bias[c] : (bf16_t)0;
-        if constexpr (SN) { psa[c] = a.sa[c]; psib[c] = a.sib[c]; }
-    }
-    __builtin_amdgcn_s_waitcnt(waitcnt_enc(0, 0));
-    const uint32_t l0 = lds_addr(lds);
-    const uint32_t lst = l0 + cp::PAR, lres = lst + NS * STG;
-    const char *stb = lds + cp::PAR, *resb = stb + NS * STG;
-
-    // staging cursor (block-uniform): item (phase, m0, n0) and K-tile of the next stage
-    int s_kt = 0, s_phase, s_n0;
-    int64_t s_m0;
-    {
-        s_phase = (int)(i0 % phases);
-        const int64_t w = i0 / phases;
-        s_m0 = (w / tilesN) * CBM;
-        s_n0 = (int)(w % tilesN) * CBN;
-    }
-    int s_slot = 0;            // ring slot of the next stage (rotating: no 64-bit modulo per step)
-    // the lane's W row offset inside a piece (8 rows of 128 B, source-swizzled chunk)
-    const int r8 = lane >> 3;
-    auto stage = [&] {
-        const int k0 = s_kt * BK, tap = k0 / a.Cin, ci0 = k0 - tap * a.Cin;
-        const uint32_t dst = lst + (uint32_t)s_slot * STG;
-#pragma unroll
-        for (int i = 0; i < PW / 2; ++i) {                  // A: im2col rows (zero page outside)
-            const int q = wave + cp::NW * i, r = q * 8 + r8;
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            glds16_v(a_src(a, s_m0 + r, tap, ci0, c), dst + q * 1024);
-        }
-        const char *wb = (const char *)(a.W + (int64_t)s_phase * a.w_pstride + (int64_t)s_n0 * K + k0);
-#pragma unroll
-        for (int i = PW / 2; i < PW; ++i) {                 // W rows
-            const int q = wave + cp::NW * i, r = q * 8 + r8 - CBM;
-            const int c = (lane & 7) ^ (((r + CBM) >> 1) & 7);
-            glds16_s(uniform_ptr(wb), (uint32_t)(r * K + c * 8) * 2, dst + q * 1024);
-        }
-        if (++s_slot == NS) s_slot = 0;
-        if (++s_kt == nk) {
-            s_kt = 0;
-            if (++s_phase == phases) {
-                s_phase = 0;
-                s_n0 += CBN;
-                if (s_n0 == a.N) { s_n0 = 0; s_m0 += CBM; }
-            }
-        }
-    };
-    // the item's residual tile: 4 rows × 256 B per piece, chunk c of row r stored at c ^ (r & 15)
-    auto stage_res = [&](int64_t m0, int n0, int phase) {
-#pragma unroll
-        for (int i = 0; i < RW; ++i) {
-            const int q = wave + cp::NW * i, r = q * 4 + (lane >> 4);
-            const int c = (lane & 15) ^ (r & 15);
-            const int64_t m = min(m0 + r, a.M - 1);
-            const int64_t row = min(max(m * a.c_stride + a.c_off + phase, (int64_t)0), a.L_out - 1);
-            glds16_v(a.res + row * a.N + n0 + c * 8, lres + q * 1024);
-        }
-    };
-
-    f32x4 acc[SM][SNT];
-#pragma unroll
-    for (int i = 0; i < SM; ++i)
-#pragma unroll
-        for (int j = 0; j < SNT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int s = 0; s < NS - 1; ++s)
-        if (s < G) stage();
-    // compute cursor
-    int kt = 0, phase = 0, n0 = 0;
-    int64_t m0 = 0;
-    {
-        phase = (int)(i0 % phases);
-        const int64_t w = i0 / phases;
-        m0 = (w / tilesN) * CBM;
-        n0 = (int)(w % tilesN) * CBN;
-    }
-    bool prev_st = false;      // previous epilogue issued exactly KST stores per wave
-    int slot = 0;
-    for (int64_t g = 0; g < G; ++g) {
-        const int64_t left = G - 1 - g;   // K-steps after this one
-        const int newer = left < NS - 2 ? (int)left : NS - 2;
-        // residual pieces (issued at this item's first step, before that step's refill) are
-        // younger than stage g when g ≥ item start + 1 and stage g was issued at or before it
-        const bool rs = RES && kt >= 1 && kt <= NS - 2;
-        const bool st = prev_st && kt <= NS - 2;
-        const int extra = (rs ? RW : 0) + (st ? KST : 0);
-#define CP_W(E)                                                    \
-    do {                                                           \
-        if (newer == 2) wait_vm_lgkm0<2 * PW + (E)>();             \
-        else if (newer == 1) wait_vm_lgkm0<PW + (E)>();            \
-        else wait_vm_lgkm0<(E)>();                                 \
-    } while (0)
-        if (extra == RW + KST) CP_W(RW + KST);
-        else if (extra == KST) CP_W(KST);
-        else if (extra == RW) CP_W(RW);
-        else CP_W(0);
-#undef CP_W
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (RES && kt == 0) stage_res(m0, n0, phase);
-        if (g + NS - 1 < G) stage();
-        const char *b = stb + slot * STG;
-        if (++slot == NS) slot = 0;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xf[SM], wf[SNT];
-#pragma unroll
-            for (int i = 0; i < SM; ++i) xf[i] = *(const bf16x8 *)(b + swz(wm * TM + i * 16 + fr, ks * 4 + fc));
-#pragma unroll
-            for (int j = 0; j < SNT; ++j) wf[j] = *(const bf16x8 *)(b + swz(CBM + wn * TN + j * 16 + fr, ks * 4 + fc));
-#pragma unroll
-            for (int i = 0; i < SM; ++i)
-#pragma unroll
-                for (int j = 0; j < SNT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-        }
-        if (++kt < nk) continue;
-        // epilogue: the residual image retired (younger: the ≤ NS − 1 stages issued after
-        // stage g, all after it), then visible to every wave
-        if (RES) {
-            const int en = left < NS - 1 ? (int)left : NS - 1;
-            if (en == 2) wait_vm_lgkm0<2 * PW>();
-            else if (en == 1) wait_vm_lgkm0<PW>();
-            else wait_vm_lgkm0<0>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        }
-        const int n = n0 + wn * TN + (odd ? 16 : 0) + (fc >> 1) * 8;
-        float bb[8];
-        unpack8(*(const uint4 *)(pbias + n), bb);
-#pragma unroll
-        for (int i = 0; i < SM; ++i) {
-            float o[8];
-            pair8(acc[i][0], acc[i][1], odd, o);
-            acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int rl = wm * TM + i * 16 + fr;
-            const int64_t m = m0 + rl;
-            const int64_t row = m * a.c_stride + a.c_off + phase;
-            add_n<8>(o, bb);
-            rbf_n<8>(o);
-            if constexpr (RES) {
-                float rr[8];
-                const int cl = (n - n0) >> 3;           // 16-B chunk of the item's 128 columns
-                unpack8(*(const uint4 *)(resb + rl * 256 + ((cl ^ (rl & 15)) << 4)), rr);
-                add_n<8>(o, rr);
-                rbf_n<8>(o);
-            }
-            float sn[8];
-            if constexpr (SN) {
-                snake_n<8>(o, psa + n, psib + n, sn);
-            }
-            if (m < a.M && row >= 0 && row < a.L_out) {
-                if constexpr (RAW) *(uint4 *)(a.out + row * a.N + n) = pack8(o);
-                if constexpr (SN) *(uint4 *)(a.out_s + row * a.N + n) = pack8(sn);
-            }
-        }
-        prev_st = m0 + CBM <= a.M && m0 * a.c_stride + a.c_off + phase >= 0 &&
-                  (m0 + CBM - 1) * a.c_stride + a.c_off + phase < a.L_out;
-        kt = 0;
-        if (++phase == phases) {
-            phase = 0;
-            n0 += CBN;
-            if (n0 == a.N) { n0 = 0; m0 += CBM; }
-        }
-    }
-}
-
-// Fused Oobleck residual unit at C = 128 (vae_model.py:62-87):
-//   y_s = snake2(conv7_dil(x_s) + b1)            (kept in LDS, never in HBM)
-//   x'  = x + (W2·y_s + b2);  x'_s = snake_next(x')
-// One 128-position tile per block: the k=7 GEMM (K = 896) through the
-// 2-stage glds ring, its epilogue writes y_s into the swizzled LDS image of
-// the k=1 GEMM's A operand, W2 (128×128) is staged alongside, then the k=1
-// GEMM (K = 128) and the residual / next-Snake epilogue.
-template <bool RAW>
-__global__ __launch_bounds__(256, 2) void resunit128_kernel(ResUnitArgs u) {
-    constexpr int BM = 128, STAGE = ConvTile::STAGE;
-    __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
-    const ConvArgs &a = u.c1;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int64_t tilesM = (a.M + BM - 1) / BM;
-    const int64_t m0 = (int64_t)xcd_remap(blockIdx.x, (int)tilesM) * BM;
-    const int K = a.taps * 128;
-    int rowq[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rowq[i] = (wave + 4 * i) * 8 + (lane >> 3);
-    auto stage = [&](int buf, int k0) {
-        char *b = lds + buf * STAGE;
-        const int tap = k0 >> 7, ci0 = k0 & 127;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int r = rowq[i];
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            const bf16_t *src = r < BM ? a_src(a, m0 + r, tap, ci0, c) : a.W + (int64_t)(r - BM) * K + k0 + c * 8;
-            glds16(src, b + (wave + 4 * i) * 1024);
-        }
-    };
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int nk = K / BK;
-    stage(0, 0);
-    const int fr = lane & 15, fc = lane >> 4;
-    for (int kt = 0; kt < nk; ++kt) {
-        wait_vm_lgkm0<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BK);
-        const char *b = lds + (kt & 1) * STAGE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xf[4], wf[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                xf[i] = *(const bf16x8 *)(b + swz(wm * 64 + i * 16 + fr, ks * 4 + fc));
-                wf[i] = *(const bf16x8 *)(b + swz(BM + wn * 64 + i * 16 + fr, ks * 4 + fc));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-        }
-    }
-    // all waves done reading the ring; reuse it: [y_s k 0..63 | y_s k 64..127 | W2 k 0..63 | W2 k 64..127]
-    wait_vm_lgkm0<0>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    char *ys = lds;                 // 2 × 16 KiB
-    char *w2 = lds + 2 * 16384;     // 2 × 16 KiB
-    // W2 [128][128] → 2 k-halves of [128 rows][64]: 32 glds, 8 per wave
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int qq = wave + 4 * i;        // 0..31: half = qq >> 4, rows 8(qq&15)..+7
-        const int h = qq >> 4, r = (qq & 15) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        glds16(u.W2 + (int64_t)r * 128 + h * 64 + c * 8, w2 + h * 16384 + (qq & 15) * 1024);
-    }
-    // epilogue 1: y_s = snake2(bf16(acc + b1)) → LDS (A image of the k=1 GEMM)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = wm * 64 + i * 16 + fr;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int n = wn * 64 + j * 16 + fc * 4;
-            float bb[4];
-            unpack4(*(const uint2 *)(a.bias + n), bb);
-            const float4 sa = *(const float4 *)(a.sa + n);
-            const float4 sb = *(const float4 *)(a.sib + n);
-            const float sav[4] = {sa.x, sa.y, sa.z, sa.w}, sbv[4] = {sb.x, sb.y, sb.z, sb.w};
-            float o[4];
-            float t[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            add_n<4>(t, bb);
-            rbf_n<4>(t);
-            snake_n<4>(t, sav, sbv, o);
-            const int h = n >> 6, cc = (n & 63) >> 3;
-            *(uint2 *)(ys + h * 16384 + swz(row, cc) + (n & 7) * 2) = pack4(o);
-            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-    wait_vm_lgkm0<0>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    // k=1 GEMM: K = 128 = 2 halves × 2 k-steps
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xf[4], wf[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                xf[i] = *(const bf16x8 *)(ys + h * 16384 + swz(wm * 64 + i * 16 + fr, ks * 4 + fc));
-                wf[i] = *(const bf16x8 *)(w2 + h * 16384 + swz(wn * 64 + i * 16 + fr, ks * 4 + fc));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-        }
-    // epilogue 2: x' = x + bf16(acc + b2); raw (optional) + snake_next
-    const bool odd = fc & 1;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t m = m0 + wm * 64 + i * 16 + fr;
-        if (m >= a.M) continue;
-#pragma unroll
-        for (int jp = 0; jp < 2; ++jp) {
-            float o[8], bb[8], rr[8];
-            pair8(acc[i][2 * jp], acc[i][2 * jp + 1], odd, o);
-            const int n = wn * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + (fc >> 1) * 8;
-            unpack8(*(const uint4 *)(u.b2 + n), bb);
-            unpack8(*(const uint4 *)(u.x + m * 128 + n), rr);
-            add_n<8>(o, bb);
-            rbf_n<8>(o);
-            add_n<8>(o, rr);
-            rbf_n<8>(o);
-            if constexpr (RAW) *(uint4 *)(u.x + m * 128 + n) = pack8(o);
-            float sn[8];
-            snake8(o, u.sa_next + n, u.sib_next + n, sn);
-            *(uint4 *)(u.out_s + m * 128 + n) = pack8(sn);
-        }
-    }
-}
+// Removed kernels (DESIGN.md §3 keeps what each measured):
+//   * convp_kernel — the persistent counted-ring form of conv_gemm_kernel (one block per CU
+//     walking work items through a 3/4-stage LDS-DMA ring): the k = 1 residual tails 4.55 vs
+//     5.01 ms per decode on conv_gemm_kernel, the ConvTranspose phases 8.30 vs 7.44 (round 2);
+//     superseded by the ping-pong GEMM for both, decode 35.53 → 34.77 ms (round 5,
+//     `profiles/r05z_ab_vae_conv1_gemm.log`), removed.
+//   * resunit128_kernel — the first fused C = 128 residual unit (im2col k = 7 GEMM, y_s
+//     through LDS, k = 1 GEMM; one 128-row tile per block): 3.8–4.0 ms per launch, 70.9 ms
+//     over the 18 launches of that profile (`profiles/r02_baseline_kernel_stats.md`), against
+//     61.6 ms for conv7_kernel's fused arm (`profiles/r02_kernel_stats.md`), which superseded
+//     it, as ru7_kernel and then ru8_kernel did that; removed.
+//   * conv7_kernel's FUSED arm (the residual unit as a tail of the halo conv: W2 staging, the
+//     y_s LDS round trip, two barriers, the k = 1 GEMM — more than half of that kernel, decode
+//     −11 ms with the tail skipped, round 2) and its 256-row / 8-wave / 3-W-slot geometry
+//     (47.7 vs 44.5 ms per decode, round 2): removed with their template parameters.
 
 // ---------------------------------------------------------------------------
 // k=7 dilated stride-1 convolution with the INPUT WINDOW staged once per channel
 // chunk instead of an im2col tile per tap (conv_gemm_kernel fetches every input row
 // 7× through L2 and waits vmcnt(0) on a one-tile ring every K-tile).
-// Tile 256 positions × 128 output channels, 8 waves (4 M × 2 N, 64×64 wave tiles).
+// Tile 128 positions × 128 output channels, 4 waves (2 M × 2 N, 64×64 wave tiles); 80 KiB
+// LDS, so two blocks per CU, whose epilogues and main loops interleave (the epilogue VALU —
+// bias, bf16 rounding, Snake — is ≈ the MFMA time).
 // K loop: kt = cc·7 + tap over 64-channel chunks cc; per K-tile the A fragments
 // come from the window image of chunk cc (row = position − m0 + 3·dil + tap·dil −
-// 3·dil), the W tile (128 rows × 64 k) from a 3-slot ring.  One barrier per K-tile:
+// 3·dil), the W tile (128 rows × 64 k) from a 2-slot ring.  One barrier per K-tile:
 //   top of kt   own DMAs of W(kt) (and, older, window(cc)) retired — counted vmcnt,
-//               newer W(kt+1) / window(cc+1) stay in flight — then the barrier
-//   after it    stage W(kt+2) into slot (kt+2)%3 (tile kt−1's, read before the
+//               a newer window(cc+1) stays in flight — then the barrier
+//   after it    stage W(kt+1) into the other slot (tile kt−1's, read before the
 //               barrier), and at tap 0 window(cc+1) into the other window buffer
 //               (chunk cc−1's, last read at K-tile kt−1).
 // Window image: 128-B rows (64 channels), physical chunk = chunk ^ (row & 7), which
 // keeps every ds_read_b128 lane group conflict-free for ANY row offset (the tap
 // shift tap·dil misaligns the fragment rows; tools/conv_swizzle check, r02).
-// FUSED (C = 128): the residual unit — y_s = snake2(conv7 + b1) into LDS, then the
-// k=1 GEMM with W2 and x' = x + (W2·y_s + b2), snaked for the next unit.
-// Two geometries: BM = 256 / 8 waves / 3 W slots (128 KiB LDS, one block per CU) and
-// BM = 128 / 4 waves / 2 W slots (80 KiB: two blocks per CU, whose epilogues and main
-// loops interleave — the epilogue VALU (bias, bf16 rounding, Snake) is ≈ the MFMA time)
-template <int BM_>
+// Output: Snake(bf16(conv + bias)) into out_s only (the next conv's input).
 struct Conv7 {
-    static constexpr int BM = BM_, BN = 128, NW = BM / 32;
-    static constexpr int WSLOTS = BM == 256 ? 3 : 2;
-    static constexpr int WROWS = BM == 256 ? 320 : 192;      // window rows ≥ BM + 6·9
+    static constexpr int BM = 128, BN = 128, NW = BM / 32;
+    static constexpr int WSLOTS = 2;
+    static constexpr int WROWS = 192;                        // window rows ≥ BM + 6·9
     static constexpr int WIN = WROWS * 128;                  // one window buffer (64 channels)
     static constexpr int WT = BN * 128;                      // 16 KiB per W tile
-    static constexpr int LDS = 2 * WIN + WSLOTS * WT;        // 128 / 80 KiB
-    static constexpr int PWIN = WROWS / 8 / NW;              // window pieces per wave (5 / 6)
-    static constexpr int PW = BN / 8 / NW;                   // W pieces per wave (2 / 4)
+    static constexpr int LDS = 2 * WIN + WSLOTS * WT;        // 80 KiB
+    static constexpr int PWIN = WROWS / 8 / NW;              // window pieces per wave (6)
+    static constexpr int PW = BN / 8 / NW;                   // W pieces per wave (4)
     static_assert(PWIN * 8 * NW == WROWS && PW * 8 * NW == BN, "pieces split evenly over the waves");
 };
-constexpr int CONV7_BM = 128;      // rows per block of the conv7_kernel launches below
 __device__ __forceinline__ int sw7(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
-template <int BM_, bool FUSED, bool RAW>
-__global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void conv7_kernel(ConvArgs a, ResUnitArgs u) {
-    using C7 = Conv7<BM_>;
+__global__ __launch_bounds__(256, 2) void conv7_kernel(ConvArgs a) {
+    using C7 = Conv7;
     constexpr int BM = C7::BM, BN = C7::BN;
     __shared__ __attribute__((aligned(16))) char lds[C7::LDS];
     char *win = lds, *wring = lds + 2 * C7::WIN;
@@ -593,37 +259,15 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void conv7_kernel(Conv
 
     const int fr = lane & 15, fc = lane >> 4;
     const bool odd = fc & 1;
-    // residual-unit tail operands (x, b2) loaded up front: they land during the main
-    // loop (older than every DMA, so the loop's counted waits are unaffected)
-    uint4 xv[4][2], b2v[2];
-    if constexpr (FUSED) {
-#pragma unroll
-        for (int jp = 0; jp < 2; ++jp) {
-            const int n = wn * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + (fc >> 1) * 8;
-            b2v[jp] = *(const uint4 *)(u.b2 + n);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int64_t m = min(m0 + wm * 64 + i * 16 + fr, a.M - 1);
-                xv[i][jp] = *(const uint4 *)(u.x + m * 128 + n);
-            }
-        }
-    }
     stage_win(0, 0);
     stage_w(0, 0);
-    if (C7::WSLOTS == 3 && nk > 1) stage_w(1, 1);
     for (int kt = 0; kt < nk; ++kt) {
         const int cc = kt / 7, tap = kt - cc * 7;
-        // own DMAs newer than W(kt): W(kt+1) (issued at kt−1) and a window refill issued at
-        // kt−1 or kt−2 (at a tap 0, right after that iteration's W refill)
-        // (3 W slots: W(kt+1) is newer, issued at kt−1; 2 slots: W(kt+1) is staged after
-        // this wait, and only a window refill at kt−1 is newer)
-        const bool w1 = C7::WSLOTS == 3 && kt + 1 < nk;
-        const bool wn1 = (kt >= 1 && (kt - 1) % 7 == 0 && (kt - 1) / 7 + 1 < nch) ||
-                         (C7::WSLOTS == 3 && kt >= 2 && (kt - 2) % 7 == 0 && (kt - 2) / 7 + 1 < nch);
-        if (w1 && wn1) wait_vm_lgkm0<C7::PW + C7::PWIN>();
-        else if (w1) wait_vm_lgkm0<C7::PW>();
-        else if (wn1) wait_vm_lgkm0<C7::PWIN>();
-        else wait_vm_lgkm0<0>();
+        // own DMAs newer than W(kt): only a window refill issued at kt−1 (at a tap 0, right
+        // after that iteration's W refill); W(kt+1) is staged after this wait
+        const bool wn1 = kt >= 1 && (kt - 1) % 7 == 0 && (kt - 1) / 7 + 1 < nch;
+        if (!wn1) wait_vm_lgkm0<0>();
+        else wait_vm_lgkm0<C7::PWIN>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (kt + C7::WSLOTS - 1 < nk)
@@ -647,119 +291,35 @@ __global__ __launch_bounds__(BM_ * 2, BM_ == 256 ? 1 : 2) void conv7_kernel(Conv
         }
     }
 
-    if constexpr (!FUSED) {
-        // conv output → bf16 (+bias) → Snake → out_s (the next conv's input)
+    // conv output → bf16 (+bias) → Snake → out_s (the next conv's input)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t m = m0 + wm * 64 + i * 16 + fr;
-            if (m >= a.M) continue;
+    for (int i = 0; i < 4; ++i) {
+        const int64_t m = m0 + wm * 64 + i * 16 + fr;
+        if (m >= a.M) continue;
 #pragma unroll
-            for (int jp = 0; jp < 2; ++jp) {
-                float o[8];
-                pair8(acc[i][2 * jp], acc[i][2 * jp + 1], odd, o);
-                const int n = n0 + wn * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + (fc >> 1) * 8;
-                if (a.bias) {
-                    float bb[8];
-                    unpack8(*(const uint4 *)(a.bias + n), bb);
-                    add_n<8>(o, bb);
-                }
-                rbf_n<8>(o);
-                float sn[8];
-                snake8(o, a.sa + n, a.sib + n, sn);
-                *(uint4 *)(a.out_s + m * a.N + n) = pack8(sn);
-            }
-        }
-    } else {
-        // residual unit tail (C = 128): every wave done with the window / ring
-        wait_vm_lgkm0<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        constexpr int YH = BM * 128;    // y_s image: 2 k-halves × [BM rows][128 B]
-        char *ys = lds;
-        char *w2 = lds + 2 * YH;        // W2: 2 k-halves × [128 rows][128 B] = 32 KiB
-        static_assert(2 * YH + 32768 <= C7::LDS, "residual-unit tail must fit the LDS");
-        // W2 [128][128] → 2 k-halves: 32 glds
-#pragma unroll
-        for (int i = 0; i < 32 / C7::NW; ++i) {
-            const int qq = wave + C7::NW * i;  // 0..31: half = qq >> 4, rows 8(qq&15)..+7
-            const int h = qq >> 4, r = (qq & 15) * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ (r & 7);
-            glds16(u.W2 + (int64_t)r * 128 + h * 64 + c * 8, w2 + h * 16384 + (qq & 15) * 1024);
-        }
-        // epilogue 1: y_s = snake2(bf16(acc + b1)) → LDS (A image of the k=1 GEMM)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = wm * 64 + i * 16 + fr;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = wn * 64 + j * 16 + fc * 4;
-                float bb[4];
-                unpack4(*(const uint2 *)(a.bias + n), bb);
-                const float4 sa = *(const float4 *)(a.sa + n);
-                const float4 sb = *(const float4 *)(a.sib + n);
-                const float sav[4] = {sa.x, sa.y, sa.z, sa.w}, sbv[4] = {sb.x, sb.y, sb.z, sb.w};
-                float o[4];
-                float t[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                add_n<4>(t, bb);
-                rbf_n<4>(t);
-                snake_n<4>(t, sav, sbv, o);
-                const int h = n >> 6, cc = (n & 63) >> 3;
-                *(uint2 *)(ys + h * YH + sw7(row, cc) + (n & 7) * 2) = pack4(o);
-                acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-        wait_vm_lgkm0<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        // k=1 GEMM: K = 128 = 2 halves × 2 k-steps
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                bf16x8 xf[4], wf[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    xf[i] = *(const bf16x8 *)(ys + h * YH + sw7(wm * 64 + i * 16 + fr, ks * 4 + fc));
-                    wf[i] = *(const bf16x8 *)(w2 + h * 16384 + sw7(wn * 64 + i * 16 + fr, ks * 4 + fc));
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-            }
-        // epilogue 2: x' = x + bf16(acc + b2); raw (optional) + snake_next
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t m = m0 + wm * 64 + i * 16 + fr;
-            if (m >= a.M) continue;
-#pragma unroll
-            for (int jp = 0; jp < 2; ++jp) {
-                float o[8], bb[8], rr[8];
-                pair8(acc[i][2 * jp], acc[i][2 * jp + 1], odd, o);
-                const int n = wn * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + (fc >> 1) * 8;
-                unpack8(b2v[jp], bb);
-                unpack8(xv[i][jp], rr);
+        for (int jp = 0; jp < 2; ++jp) {
+            float o[8];
+            pair8(acc[i][2 * jp], acc[i][2 * jp + 1], odd, o);
+            const int n = n0 + wn * 64 + (2 * jp + (odd ? 1 : 0)) * 16 + (fc >> 1) * 8;
+            if (a.bias) {
+                float bb[8];
+                unpack8(*(const uint4 *)(a.bias + n), bb);
                 add_n<8>(o, bb);
-                rbf_n<8>(o);
-                add_n<8>(o, rr);
-                rbf_n<8>(o);
-                if constexpr (RAW) *(uint4 *)(u.x + m * 128 + n) = pack8(o);
-                float sn[8];
-                snake8(o, u.sa_next + n, u.sib_next + n, sn);
-                *(uint4 *)(u.out_s + m * 128 + n) = pack8(sn);
             }
+            rbf_n<8>(o);
+            float sn[8];
+            snake8(o, a.sa + n, a.sib + n, sn);
+            *(uint4 *)(a.out_s + m * a.N + n) = pack8(sn);
         }
     }
 }
 
 // ---------------------------------------------------------------------------
+// ru8_kernel's bit-exact oracle (ACEHIP_RU7=1): test_vae_resunit_c128 asserts that ru8_kernel
+// equals this kernel bit for bit, and no other implementation accumulates in the same order.
 // Persistent, software-pipelined Oobleck residual unit at C = 128 (vae_model.py:62-87):
 //   y_s = snake2(conv7_dil(x_s) + b1);  x' = x + (W2·y_s + b2);  out_s = snake_next(x')
-// conv7_kernel<FUSED> runs one tile per block; its per-tile tail (W2 staging, epilogue
-// parameter loads, the y_s LDS round trip, two barriers, the k=1 GEMM, the stores) measured
-// more than half of the kernel (r02: decode −11 ms with the tail skipped).  Here every block
-// walks a contiguous range of 128-row tiles:
+// Every block walks a contiguous range of 128-row tiles:
 //  * each wave owns 32 rows × all 128 channels, so y_s never leaves registers: the k=7
 //    accumulators (lane: row fr, channels 16j + 4fc + r) ARE the B operand of the k=1 MFMA
 //    once W2's columns are permuted within each 32-block (permute_k1_kernel);
@@ -1826,22 +1386,6 @@ __global__ void cast_bf16_f32_kernel(const bf16_t *s, float *d, int64_t n) {
     if (i < n) d[i] = bf2f(s[i]);
 }
 
-// ACEHIP_CONV7=0 keeps the k=7 convolutions on the im2col conv_gemm / resunit128
-// kernels (A/B knob for the halo-staged conv7_kernel)
-bool use_conv7() { return knobs().conv7 != 0; }
-
-// Which of the remaining convs run on the persistent counted-ring convp_kernel:
-// default the k = 1 convs (C ≥ 256, residual epilogue), ACEHIP_CONVP=1 every eligible conv,
-// =0 none.  Per-kernel rocprof of a 240 s decode (r02): k = 1 convs 4.55 vs 5.01 ms on
-// conv_gemm_kernel, the ConvTranspose phases 8.30 vs 7.44 ms (so they stay there)
-bool use_convp(const ConvArgs &a, int phases) {
-    const int v = knobs().convp;
-    return v == 1 || (v == 2 && a.taps == 1 && phases == 1);
-}
-
-// C = 128 residual units: ACEHIP_RU7=2 (default) ru8_kernel, 1 ru7_kernel, 0 conv7_kernel<FUSED> (A/B)
-bool use_ru7() { return knobs().ru7 != 0; }
-
 // launch(RES, RAW, SN) with the integral constants of a conv's epilogue: a residual or none; the
 // raw output, the Snake output or both
 template <typename F>
@@ -1903,32 +1447,26 @@ int conv_gemm(const ConvArgs &a, int phases, hipStream_t s) {
         return gemm_conv(as_gemm(2, 1, -1, phases, a.c_off), s);
     }
     // k = 1 convs (the C ≥ 256 residual units' second conv, with the residual) as a plain GEMM on
-    // the ping-pong tile (ACEHIP_CONVP=3)
-    if (knobs().convp == 3 && phases == 1 && a.taps == 1 && a.a_stride == 1 && a.a_off == 0 && a.c_stride == 1 &&
+    // the ping-pong tile (ACEHIP_CONVP=0: conv_gemm_kernel)
+    if (knobs().convp != 0 && phases == 1 && a.taps == 1 && a.a_stride == 1 && a.a_off == 0 && a.c_stride == 1 &&
         a.c_off == 0 && a.L_in == a.M && a.L_out == a.M && a.N % 256 == 0 && a.M < (1ll << 31)) {
         GemmArgs g = as_gemm(1, 1, 0, 1, 0);
         g.res = a.res; g.ldr = a.N;
         return gemm_conv(g, s);
     }
-    if (use_conv7() && k7) {
-        const int64_t t7 = ((a.M + CONV7_BM - 1) / CONV7_BM) * (a.N / 128);
+    // the k = 7 convs left: an input without the padded layout (the decoder's first conv), N not a
+    // multiple of 256, or ACEHIP_CONV7=1
+    if (k7) {
+        const int64_t t7 = ((a.M + Conv7::BM - 1) / Conv7::BM) * (a.N / Conv7::BN);
         if (t7 >= (1ll << 31)) return fail(-1, "conv_gemm: grid too large");
-        conv7_kernel<CONV7_BM, false, false><<<(unsigned)t7, CONV7_BM * 2, 0, s>>>(a, ResUnitArgs{});
+        conv7_kernel<<<(unsigned)t7, 256, 0, s>>>(a);
         HIP_TRY(hipGetLastError());
         return 0;
     }
+    // everything else: the strided convs, k = 3, and what the knobs or the shapes kept off the GEMM
     const int64_t tiles = ((a.M + BM - 1) / BM) * (a.N / BN);
     if (tiles >= (1ll << 31)) return fail(-1, "conv_gemm: grid too large");
     const bool rs = a.res != nullptr, raw = a.out != nullptr, sn = a.out_s != nullptr;
-    if (use_convp(a, phases) && a.taps * a.Cin / BK >= 3 && a.N <= cp::MAXN) {   // ≥ 3 K-tiles per item (vmcnt bookkeeping)
-        const int64_t items = tiles * phases;
-        const int nb = (int)std::min<int64_t>(items, device_cus());
-        with_epilogue(rs, raw, sn, [&](auto RES, auto RAW, auto SN) {
-            convp_kernel<RES.value, RAW.value, SN.value><<<nb, 512, 0, s>>>(a, items, phases);
-        });
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
     dim3 grid((unsigned)tiles, phases);
     with_epilogue(rs, raw, sn, [&](auto RES, auto RAW, auto SN) {
         conv_gemm_kernel<RES.value, RAW.value, SN.value><<<grid, 256, 0, s>>>(a);
@@ -1941,20 +1479,26 @@ int resunit128(const ResUnitArgs &u, hipStream_t s) {
     const ConvArgs &a = u.c1;
     if (a.Cin != 128 || a.N != 128 || a.taps != 7 || !a.zero || !a.bias || !a.sa) return fail(-1, "resunit128: args");
     if (u.x == u.out_s || a.in == u.out_s) return fail(-1, "resunit128: out_s must not alias x / x_s");
-    // what ru8_kernel and ru7_kernel take: the permuted W2, a "same" k = 7 conv, its halo in the
-    // input's zero rows
-    const bool padded7 = u.W2p && u.in_zero_pad && a.dil <= 9 && a.a_off == -3 * a.dil && a.L_in == a.M;
-    if (u.snake_in && !(knobs().ru7 == 2 && padded7)) return fail(-1, "resunit128: snake_in runs on ru8_kernel only");
-    if (knobs().ru7 == 2 && padded7) {
+    // what ru8_kernel and ru7_kernel take (every C = 128 unit of the VAE and the unit hook meet it;
+    // no slower kernel stands behind them)
+    if (!u.W2p) return fail(-1, "resunit128: W2 with permuted columns (permute_k1_weight) required");
+    if (!u.in_zero_pad) return fail(-1, "resunit128: the input must be a zero-padded activation buffer (in_zero_pad)");
+    if (a.dil > 9 || a.a_off != -3 * a.dil || a.L_in != a.M)
+        return fail(-1, "resunit128: a \"same\" k = 7 conv with dil <= 9 required (dil=" + std::to_string(a.dil) + ")");
+    const int ru = knobs().ru7;
+    if (ru != 1 && ru != 2) return fail(-1, "resunit128: ACEHIP_RU7 must be 2 (ru8_kernel) or 1 (ru7_kernel)");
+    if (u.snake_in && ru != 2) return fail(-1, "resunit128: snake_in runs on ru8_kernel only");
+    if (!u.snake_in || !u.keep_raw) {
+        if (!u.out_s || !u.sa_next || !u.sib_next) return fail(-1, "resunit128: out_s and the next Snake's parameters");
+    }
+    if (u.snake_in && (!u.sa_in || !u.sib_in || (u.keep_raw && (!u.x_out || u.x_out == u.x)) || a.in != u.x))
+        return fail(-1, "resunit128: snake_in needs sa_in / sib_in, in == x and a separate x_out");
+    // the k = 7 halo past the end reads kActPadRows zero rows behind the input
+    HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * 128), 0, (size_t)kActPadRows * 256, s));
+    if (ru == 2) {
         const int64_t nt = (a.M + ru8::BM - 1) / ru8::BM;
         const int nb = (int)std::min<int64_t>(nt, (int64_t)device_cus());
-        HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * 128), 0, (size_t)kActPadRows * 256, s));
-        if (!u.snake_in || !u.keep_raw) {
-            if (!u.out_s || !u.sa_next || !u.sib_next) return fail(-1, "resunit128: out_s and the next Snake's parameters");
-        }
         if (u.snake_in) {
-            if (!u.sa_in || !u.sib_in || (u.keep_raw && (!u.x_out || u.x_out == u.x)) || a.in != u.x)
-                return fail(-1, "resunit128: snake_in needs sa_in / sib_in, in == x and a separate x_out");
             if (u.keep_raw) ru8_kernel<true, true><<<nb, 320 + 64 * ru8::NWH, 0, s>>>(u, nt);
             else ru8_kernel<false, true><<<nb, 320 + 64 * ru8::NWH, 0, s>>>(u, nt);
         } else if (u.keep_raw) {
@@ -1962,30 +1506,12 @@ int resunit128(const ResUnitArgs &u, hipStream_t s) {
         } else {
             ru8_kernel<false><<<nb, 384, 0, s>>>(u, nt);
         }
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (use_ru7() && padded7) {
+    } else {
         const int64_t nt = (a.M + ru::BM - 1) / ru::BM;
         const int nb = (int)std::min<int64_t>(nt, 2 * (int64_t)device_cus());
-        // the k=7 halo past the end reads kActPadRows zero rows behind the input
-        HIP_TRY(hipMemsetAsync((void *)(a.in + a.L_in * 128), 0, (size_t)kActPadRows * 256, s));
         if (u.keep_raw) ru7_kernel<true><<<nb, 256, 0, s>>>(u, nt);
         else ru7_kernel<false><<<nb, 256, 0, s>>>(u, nt);
-        HIP_TRY(hipGetLastError());
-        return 0;
     }
-    if (use_conv7() && a.dil <= 9 && a.a_off == -3 * a.dil && a.L_in == a.M) {
-        const int64_t t7 = (a.M + CONV7_BM - 1) / CONV7_BM;
-        if (u.keep_raw) conv7_kernel<CONV7_BM, true, true><<<(unsigned)t7, CONV7_BM * 2, 0, s>>>(a, u);
-        else conv7_kernel<CONV7_BM, true, false><<<(unsigned)t7, CONV7_BM * 2, 0, s>>>(a, u);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const int64_t tiles = (a.M + 127) / 128;
-    if (tiles >= (1ll << 31)) return fail(-1, "resunit128: grid too large");
-    if (u.keep_raw) resunit128_kernel<true><<<(unsigned)tiles, 256, 0, s>>>(u);
-    else resunit128_kernel<false><<<(unsigned)tiles, 256, 0, s>>>(u);
     HIP_TRY(hipGetLastError());
     return 0;
 }

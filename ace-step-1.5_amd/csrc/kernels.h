@@ -28,9 +28,9 @@ struct Knobs {
     int gemm_cus = 0;         // ACEHIP_GEMM_CUS: CU count the GEMM tile planner uses (0: the device's; tests plan multi-round grids at small shapes)
     int gemm_hp_tail = 1;     // ACEHIP_GEMM_HPTAIL: head-post GEMMs as a tail split (256-row main rounds + a 128-row tail round) where the cost model prefers it
     int convt = 1;            // ACEHIP_CONVT: 1 ConvTranspose (N % 256 == 0, padded input) as an implicit GEMM, 0 conv_gemm_kernel
-    int conv7 = 2;            // ACEHIP_CONV7: k = 7 VAE convs — 2 implicit GEMM on the ping-pong tile (C ≥ 256, padded input), 1 halo-staged conv7_kernel
-    int convp = 3;            // ACEHIP_CONVP: 0 none, 1 all, 2 k = 1 convs on convp_kernel, 3 k = 1 convs with N % 256 == 0 on the ping-pong GEMM (the rest on conv_gemm_kernel)
-    int ru7 = 2;              // ACEHIP_RU7: C = 128 residual unit — 2 ru8_kernel (256-row tiles), 1 ru7_kernel, 0 conv7
+    int conv7 = 2;            // ACEHIP_CONV7: k = 7 VAE convs — 2 implicit GEMM on the ping-pong tile (C ≥ 256, padded input; the rest on conv7_kernel), 1 halo-staged conv7_kernel everywhere
+    int convp = 1;            // ACEHIP_CONVP: nonzero — the k = 1 residual tails with N % 256 == 0 on the ping-pong GEMM, 0 on conv_gemm_kernel
+    int ru7 = 2;              // ACEHIP_RU7: C = 128 residual unit — 2 ru8_kernel (256-row tiles), 1 ru7_kernel, ru8_kernel's bit-exact oracle
     int vae_snake_in = 1;     // ACEHIP_VAE_SNAKE_IN: C = 128 decoder blocks without x_s tensors (ru8 SIN)
     int cross_fuse = 1;       // ACEHIP_CROSS_FUSE: the conditional rows' cross-Q projection and cross-attention as one launch (cross_q_attn_kernel) where the shape allows, 0: two launches
     int kv_group_kib = 262144; // ACEHIP_KV_GROUP_KIB: cross-K/V scratch bound at dit_create (tests force small groups)

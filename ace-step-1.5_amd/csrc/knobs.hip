@@ -40,7 +40,7 @@ Knobs read_env() {
     k.gemm_persist = env_int("ACEHIP_GEMM_PERSIST", 1);
     k.gemm_saddr = env_int("ACEHIP_GEMM_SADDR", 1);
     k.gemm_cus = env_int("ACEHIP_GEMM_CUS", 0);
-    k.convp = env_int("ACEHIP_CONVP", 3);
+    k.convp = env_int("ACEHIP_CONVP", 1);
     k.ru7 = env_int("ACEHIP_RU7", 2);
     k.kv_group_kib = env_int("ACEHIP_KV_GROUP_KIB", 262144);
     k.vae_snake_in = env_int("ACEHIP_VAE_SNAKE_IN", 1);

@@ -38,7 +38,7 @@ struct SnakeP {
 struct ResU {
     SnakeP s1, s2;
     ConvL c1, c2;
-    bf16_t *W2p = nullptr;   // C = 128: c2 weights permuted for ru7_kernel
+    bf16_t *W2p = nullptr;   // C = 128: c2 weights permuted for ru8_kernel (and ru7_kernel)
     int dil = 1;
 };
 struct DecBlk {
@@ -166,21 +166,31 @@ int run_conv(const bf16_t *zero, const ConvL &c, const bf16_t *in, int64_t L_in,
     return conv_gemm(a, phases, s);
 }
 
+// what every C = 128 residual-unit launch shares: the k = 7 conv on `in` (one of the handle's
+// padded activation buffers, or the unit hook's copy of that layout), W2 permuted, the raw x and
+// the next Snake; the caller sets the outputs (out_s / x_out), keep_raw and snake_in
+ResUnitArgs res_unit_args(const bf16_t *zero, const ResU &r, int64_t L, const bf16_t *in, bf16_t *x, const SnakeP &next) {
+    ResUnitArgs u{};
+    ConvArgs &a = u.c1;
+    a.in = in; a.L_in = L; a.Cin = 128; a.W = r.c1.Wp; a.bias = r.c1.bias;
+    a.sa = r.s2.a; a.sib = r.s2.ib; a.L_out = L; a.N = 128; a.M = L;
+    a.taps = 7; a.dil = r.dil; a.a_stride = 1; a.a_off = -3 * r.dil; a.c_stride = 1; a.c_off = 0;
+    a.zero = zero;
+    u.W2p = r.W2p; u.b2 = r.c2.bias; u.x = x;
+    u.in_zero_pad = 1;
+    u.sa_next = next.a; u.sib_next = next.ib;
+    return u;
+}
+
 // residual unit on (x raw in X, x_s in cur): leaves x in X (if keep_raw) and next-snaked x in cur
 int res_unit(const bf16_t *zero, const ResU &r, int64_t L, bf16_t *X, bf16_t *cur, bf16_t *other, const SnakeP &next, bool keep_raw,
              hipStream_t s) {
     int rc;
     if (r.c1.cin == 128) {
-        // fused k=7 → Snake → k=1 → residual; y_s never leaves LDS
-        ResUnitArgs u{};
-        ConvArgs &a = u.c1;
-        a.in = cur; a.L_in = L; a.Cin = 128; a.W = r.c1.Wp; a.bias = r.c1.bias;
-        a.sa = r.s2.a; a.sib = r.s2.ib; a.L_out = L; a.N = 128; a.M = L;
-        a.taps = 7; a.dil = r.dil; a.a_stride = 1; a.a_off = -3 * r.dil; a.c_stride = 1; a.c_off = 0;
-        a.zero = zero;
-        u.W2 = r.c2.Wp; u.W2p = r.W2p; u.b2 = r.c2.bias; u.x = X; u.out_s = other;
-        u.in_zero_pad = 1;   // cur is h->P or h->Q
-        u.sa_next = next.a; u.sib_next = next.ib; u.keep_raw = keep_raw ? 1 : 0;
+        // fused k=7 → Snake → k=1 → residual; y_s never leaves the registers
+        ResUnitArgs u = res_unit_args(zero, r, L, cur, X, next);
+        u.out_s = other;
+        u.keep_raw = keep_raw ? 1 : 0;
         if ((rc = resunit128(u, s))) return rc;
         // the snaked output is in `other`: copy-free hand-back by swapping roles is done by the caller
         return 1;   // signals "output in other"
@@ -215,17 +225,9 @@ int dec_block_snake_in(acehip_vae *h, int j, int64_t &L, bf16_t *&X, bf16_t *&cu
         const ResU &r = bk.res[u];
         const SnakeP &next = j + 1 < n ? h->dec[j + 1].snake : h->dsnake;
         bf16_t *in = bufs[u], *out = bufs[(u + 1) % 3];
-        ResUnitArgs ua{};
-        ConvArgs &a = ua.c1;
-        a.in = in; a.L_in = L; a.Cin = 128; a.W = r.c1.Wp; a.bias = r.c1.bias;
-        a.sa = r.s2.a; a.sib = r.s2.ib; a.L_out = L; a.N = 128; a.M = L;
-        a.taps = 7; a.dil = r.dil; a.a_stride = 1; a.a_off = -3 * r.dil; a.c_stride = 1; a.c_off = 0;
-        a.zero = h->zero;
-        ua.W2 = r.c2.Wp; ua.W2p = r.W2p; ua.b2 = r.c2.bias; ua.x = in;
-        ua.in_zero_pad = 1;
+        ResUnitArgs ua = res_unit_args(h->zero, r, L, in, in, next);   // (next: read only by the last unit, out_s)
         ua.snake_in = 1; ua.sa_in = r.s1.a; ua.sib_in = r.s1.ib;
         ua.keep_raw = u < 2 ? 1 : 0;
-        ua.sa_next = next.a; ua.sib_next = next.ib;     // read only by the last unit (out_s)
         if (u < 2) ua.x_out = out;
         else ua.out_s = out;
         if ((rc = resunit128(ua, s))) return rc;
@@ -234,6 +236,41 @@ int dec_block_snake_in(acehip_vae *h, int j, int64_t &L, bf16_t *&X, bf16_t *&cu
     cur = bufs[0];
     X = bufs[1];
     other = bufs[2];
+    return 0;
+}
+
+// the decoder's conv1 and its first n_blocks blocks on one song's latents z [Cz][T] (channels
+// first); returns the buffer that holds the snaked output, L rows of it
+int dec_blocks(acehip_vae *h, const bf16_t *z, int T, int n_blocks, bf16_t *&cur, int64_t &L, hipStream_t s) {
+    const int n = h->cfg.n_blocks;
+    int rc;
+    bf16_t *X = h->X, *other = h->Q;
+    cur = h->P;
+    if ((rc = cf_to_nlc(z, h->cfg.latent_channels, T, X, s))) return rc;
+    // conv1 (k7) → snaked by block 0's snake1
+    if ((rc = run_conv(h->zero, h->dconv1, X, T, T, 7, 1, 1, -3, 1, 0, T, nullptr, cur, &h->dec[0].snake, nullptr, 1, s)))
+        return rc;
+    L = T;
+    for (int j = 0; j < n_blocks; ++j) {
+        const auto &bk = h->dec[j];
+        const int st = bk.stride, pad = (st + 1) / 2;
+        if (snake_in_block(bk)) {
+            if ((rc = dec_block_snake_in(h, j, L, X, cur, other, s))) return rc;
+            continue;
+        }
+        // ConvTranspose1d as `st` phase GEMMs → raw x (residual) + snaked x for res_unit1
+        if ((rc = run_conv(h->zero, bk.convT, cur, L, L + 1, 2, 1, 1, -1, st, -pad, L * st, X, other, &bk.res[0].s1,
+                           nullptr, st, s, 1)))
+            return rc;
+        L *= st;
+        std::swap(cur, other);
+        for (int u = 0; u < 3; ++u) {
+            const SnakeP &next = u < 2 ? bk.res[u + 1].s1 : (j + 1 < n ? h->dec[j + 1].snake : h->dsnake);
+            rc = res_unit(h->zero, bk.res[u], L, X, cur, other, next, u < 2, s);
+            if (rc == 1) std::swap(cur, other);
+            else if (rc) return rc;
+        }
+    }
     return 0;
 }
 
@@ -419,32 +456,9 @@ int acehip_vae_decode(acehip_vae *h, const void *z, int B, int T, void *wav, voi
     for (int b = 0; b < B; ++b) {
         const bf16_t *zb = (const bf16_t *)z + (int64_t)b * Cz * T;
         float *wb = (float *)wav + (int64_t)b * h->cfg.audio_channels * Lout;
-        bf16_t *X = h->X, *cur = h->P, *other = h->Q;
-        if ((rc = cf_to_nlc(zb, Cz, T, X, s))) return rc;
-        // conv1 (k7) → snaked by block 0's snake1
-        if ((rc = run_conv(h->zero, h->dconv1, X, T, T, 7, 1, 1, -3, 1, 0, T, nullptr, cur, &h->dec[0].snake, nullptr, 1, s)))
-            return rc;
-        int64_t L = T;
-        for (int j = 0; j < n; ++j) {
-            const auto &bk = h->dec[j];
-            const int st = bk.stride, pad = (st + 1) / 2;
-            if (snake_in_block(bk)) {
-                if ((rc = dec_block_snake_in(h, j, L, X, cur, other, s))) return rc;
-                continue;
-            }
-            // ConvTranspose1d as `st` phase GEMMs → raw x (residual) + snaked x for res_unit1
-            if ((rc = run_conv(h->zero, bk.convT, cur, L, L + 1, 2, 1, 1, -1, st, -pad, L * st, X, other, &bk.res[0].s1,
-                               nullptr, st, s, 1)))
-                return rc;
-            L *= st;
-            std::swap(cur, other);
-            for (int u = 0; u < 3; ++u) {
-                const SnakeP &next = u < 2 ? bk.res[u + 1].s1 : (j + 1 < n ? h->dec[j + 1].snake : h->dsnake);
-                rc = res_unit(h->zero, bk.res[u], L, X, cur, other, next, u < 2, s);
-                if (rc == 1) std::swap(cur, other);
-                else if (rc) return rc;
-            }
-        }
+        bf16_t *cur;
+        int64_t L;
+        if ((rc = dec_blocks(h, zb, T, n, cur, L, s))) return rc;
         if ((rc = conv_out(cur, L, h->cfg.decoder_channels, h->dconv2_w, h->cfg.audio_channels, wb, s))) return rc;
     }
     return 0;
@@ -453,39 +467,16 @@ int acehip_vae_decode(acehip_vae *h, const void *z, int B, int T, void *wav, voi
 int acehip_vae_decode_blocks(acehip_vae *h, const void *z, int T, int n_blocks, void *act, void *stream) {
     if (!h || !z || !act) return fail(ACEHIP_E_ARG, "null argument");
     if (!h->finalized) return fail(ACEHIP_E_STATE, "vae_decode_blocks before finalize");
-    const int n = h->cfg.n_blocks, Cz = h->cfg.latent_channels;
-    if (T <= 0 || T > h->cfg.max_T || n_blocks < 0 || n_blocks > n)
+    if (T <= 0 || T > h->cfg.max_T || n_blocks < 0 || n_blocks > h->cfg.n_blocks)
         return fail(ACEHIP_E_ARG, "vae_decode_blocks: T or n_blocks out of range");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     // the same launches as acehip_vae_decode, stopped after block n_blocks
-    bf16_t *X = h->X, *cur = h->P, *other = h->Q;
-    if ((rc = cf_to_nlc((const bf16_t *)z, Cz, T, X, s))) return rc;
-    if ((rc = run_conv(h->zero, h->dconv1, X, T, T, 7, 1, 1, -3, 1, 0, T, nullptr, cur, &h->dec[0].snake, nullptr, 1, s)))
-        return rc;
-    int64_t L = T, C = h->dec[0].cin;
-    for (int j = 0; j < n_blocks; ++j) {
-        const auto &bk = h->dec[j];
-        const int st = bk.stride, pad = (st + 1) / 2;
-        if (snake_in_block(bk)) {
-            if ((rc = dec_block_snake_in(h, j, L, X, cur, other, s))) return rc;
-            C = bk.cout;
-            continue;
-        }
-        if ((rc = run_conv(h->zero, bk.convT, cur, L, L + 1, 2, 1, 1, -1, st, -pad, L * st, X, other, &bk.res[0].s1,
-                           nullptr, st, s, 1)))
-            return rc;
-        L *= st;
-        C = bk.cout;
-        std::swap(cur, other);
-        for (int u = 0; u < 3; ++u) {
-            const SnakeP &next = u < 2 ? bk.res[u + 1].s1 : (j + 1 < n ? h->dec[j + 1].snake : h->dsnake);
-            rc = res_unit(h->zero, bk.res[u], L, X, cur, other, next, u < 2, s);
-            if (rc == 1) std::swap(cur, other);
-            else if (rc) return rc;
-        }
-    }
+    bf16_t *cur;
+    int64_t L;
+    int rc;
+    if ((rc = dec_blocks(h, (const bf16_t *)z, T, n_blocks, cur, L, s))) return rc;
+    const int64_t C = n_blocks ? h->dec[n_blocks - 1].cout : h->dec[0].cin;
     HIP_TRY(hipMemcpyAsync(act, cur, (size_t)L * C * 2, hipMemcpyDeviceToDevice, s));
     return 0;
 }

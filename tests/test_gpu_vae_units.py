@@ -161,9 +161,10 @@ def test_vae_convt_implicit_gemm(gpu_device, monkeypatch, Cin, Cout, stride, L, 
 
 @pytest.mark.parametrize("C,L,raw", [(256, 1000, True), (512, 600, False), (1024, 257, True)])
 def test_vae_conv1_residual_gemm(gpu_device, monkeypatch, C, L, raw):
-    """ACEHIP_CONVP=3: the C ≥ 256 residual units' k = 1 conv with its residual (x' = x +
-    bf16(W2·y_s + b2), raw and/or snaked) as a plain GEMM on the ping-pong tile, vs torch fp32 and
-    vs convp_kernel (ACEHIP_CONVP=2)."""
+    """ACEHIP_CONVP on (nonzero, the default): the C ≥ 256 residual units' k = 1 conv with its
+    residual (x' = x + bf16(W2·y_s + b2), raw and/or snaked) as a plain GEMM on the ping-pong tile,
+    vs torch fp32 and vs conv_gemm_kernel (ACEHIP_CONVP=0).  Both kernels round the conv output to
+    bf16, add the residual and round again; only their fp32 accumulation orders differ."""
     g = torch.Generator(device=gpu_device).manual_seed(C + L)
     x = _bf(torch.randn(L, C, device=gpu_device, generator=g))
     w = _bf(torch.randn(C, C, 1, device=gpu_device, generator=g) / math.sqrt(C))
@@ -171,9 +172,9 @@ def test_vae_conv1_residual_gemm(gpu_device, monkeypatch, C, L, raw):
     res = _bf(torch.randn(L, C, device=gpu_device, generator=g))
     alpha = _bf(torch.randn(C, device=gpu_device, generator=g) * 0.3)
     beta = _bf(torch.randn(C, device=gpu_device, generator=g) * 0.3)
-    set_knob(monkeypatch, "ACEHIP_CONVP", "3")
+    set_knob(monkeypatch, "ACEHIP_CONVP", "1")
     out, out_s = _run_conv(0, x, w, bias, res, C, 1, 1, 1, raw, alpha, beta)
-    set_knob(monkeypatch, "ACEHIP_CONVP", "2")
+    set_knob(monkeypatch, "ACEHIP_CONVP", "0")
     out0, out_s0 = _run_conv(0, x, w, bias, res, C, 1, 1, 1, raw, alpha, beta)
     torch.cuda.synchronize()
     y = res.float() + _ref_conv(0, x, w, bias, 1, 1, 1)

@@ -52,9 +52,9 @@ def algorithmic(T, snake_in=True, gemm_convs=True):
     blocks = c.decoder_block_channels()
     c0 = blocks[0][0]
     fam["conv7_kernel"] += T * c.decoder_input_channels * B + T * c0 * B + 7 * c.decoder_input_channels * c0 * B
-    # gemm_convs (ACEHIP_CONV7=2, ACEHIP_CONVT=1, round 5): the ConvTransposes and the C ≥ 256 k7
-    # convs run on gemm_pp_kernel (EPI_CONV)
-    kt = "gemm_pp_kernel" if gemm_convs else "conv_gemm_kernel"
+    # gemm_convs (ACEHIP_CONV7=2, ACEHIP_CONVT=1, ACEHIP_CONVP on, round 5): the ConvTransposes and
+    # the C ≥ 256 k7 and k1 convs run on gemm_pp_kernel (EPI_CONV)
+    kt = k1 = "gemm_pp_kernel" if gemm_convs else "conv_gemm_kernel"
     k7 = "gemm_pp_kernel" if gemm_convs else "conv7_kernel"
     L = T
     for cin, cout, s in blocks:
@@ -70,7 +70,7 @@ def algorithmic(T, snake_in=True, gemm_convs=True):
                 fam["ru8_kernel"] += (2 + (2 if keep else 1)) * L * cout * B + 8 * cout * cout * B
             else:
                 fam[k7] += 2 * L * cout * B + 7 * cout * cout * B
-                fam["convp_kernel"] += (2 + (2 if keep else 1)) * L * cout * B + cout * cout * B
+                fam[k1] += (2 + (2 if keep else 1)) * L * cout * B + cout * cout * B
     fam["conv_out_kernel"] += L * 128 * B + L * 2 * 4
     return fam
 
@@ -82,7 +82,7 @@ def main():
     p.add_argument("out_json")
     p.add_argument("--T", type=int, default=6000)
     p.add_argument("--no-snake-in", action="store_true", help="model of ACEHIP_VAE_SNAKE_IN=0")
-    p.add_argument("--no-gemm-convs", action="store_true", help="model of ACEHIP_CONV7=1 ACEHIP_CONVT=0")
+    p.add_argument("--no-gemm-convs", action="store_true", help="model of ACEHIP_CONV7=1 ACEHIP_CONVT=0 ACEHIP_CONVP=0")
     a = p.parse_args()
     F, nF = per_family(a.fetch_db, "FETCH_SIZE")
     W, nW = per_family(a.write_db, "WRITE_SIZE")
