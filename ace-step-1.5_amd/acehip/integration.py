@@ -48,7 +48,9 @@ Seams:
              call on the ``LLMHandler``, :func:`install` does not touch it — replaces it with
              :class:`~acehip.lm.HipCausalLM` (prefill + one-token decode over a K/V cache in the
              handle, vocabulary projection); the logits processors, sampling, ``generate()``
-             and scoring (``get_hf_model_for_scoring``) stay in torch.
+             and scoring (``get_hf_model_for_scoring``) stay in torch.  With ``filters=True`` the
+             handler's ``_apply_top_k_filter`` / ``_apply_top_p_filter`` (``:367-385``) are rebound
+             to :class:`~acehip.lm.HipLogitFilters` (``acehip_lm_filter``).
 
 Failure policy: by default an acehip error propagates (the request fails
 loudly, ``generate_music.py:181-190`` turns it into an error payload).  The
@@ -256,7 +258,7 @@ def install(handler, max_seconds: float = 600.0, max_batch: int = 8, fallback: b
 
 
 def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback: bool = False, runtime=None,
-               **kw) -> dict:
+               filters: bool = False, **kw) -> dict:
     """Put the 5 Hz LM's token loop on libacehip: ``llm_handler.llm`` (a transformers
     ``Qwen3ForCausalLM`` on the ``pt`` backend) becomes a :class:`~acehip.lm.HipCausalLM`.
 
@@ -267,8 +269,19 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
     error in a call is logged and that call and the rest of the generation run on the original
     module, the policy of :func:`install`.  ``runtime``: an already built
     :class:`~acehip.lm.HipLMRuntime` (or, in the host tests, a stand-in) instead of one built
-    from the model's weights."""
-    from .lm import HipCausalLM
+    from the model's weights.
+
+    ``filters=True`` (and the LM itself installed): the handler's ``_apply_top_k_filter`` and
+    ``_apply_top_p_filter`` (``llm_inference.py:367-385``, called through ``self`` by every loop)
+    are rebound on the instance to a :class:`~acehip.lm.HipLogitFilters` (``acehip_lm_filter``:
+    no sort, in place, the same tensor returned); the result carries it and the two originals
+    under ``"filters"``.  A CPU tensor (the MLX bridge), another dtype or layout, or a
+    switched-off filter goes to the original method; ``fallback=True`` covers an acehip error in
+    a filter call the same way.  A handler that lacks one of the two methods keeps both as they
+    are (logged).  ``_sample_tokens`` (temperature, softmax, multinomial), the CFG combination,
+    the FSM processor and the repetition penalty stay as they are.  With ``filters=False``
+    nothing about the handler's methods changes."""
+    from .lm import HipCausalLM, HipLogitFilters
     backend = getattr(llm_handler, "llm_backend", None)
     if backend != "pt":
         log.info("acehip install_lm: llm_backend is %r, not 'pt'; nothing installed", backend)
@@ -285,7 +298,19 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
         lm = HipCausalLM.from_reference_model(orig, max_batch=max_batch, capacity=capacity, fallback=fallback, **kw)
     llm_handler.llm = lm
     llm_handler.get_hf_model_for_scoring = lambda: orig
-    return {"lm": lm, "original": orig}
+    out = {"lm": lm, "original": orig}
+    if filters:
+        orig_k = getattr(llm_handler, "_apply_top_k_filter", None)
+        orig_p = getattr(llm_handler, "_apply_top_p_filter", None)
+        if orig_k is None or orig_p is None:
+            log.info("acehip install_lm: the handler has no _apply_top_k_filter / _apply_top_p_filter; "
+                     "the logit filters stay as they are")
+        else:
+            f = HipLogitFilters(orig_k, orig_p, fallback=fallback, max_batch=max_batch)
+            llm_handler._apply_top_k_filter = f.top_k
+            llm_handler._apply_top_p_filter = f.top_p
+            out["filters"] = {"hip": f, "top_k": orig_k, "top_p": orig_p}
+    return out
 
 
 def hip_normalize_audio(audio_data: torch.Tensor, target_db: float = -1.0) -> torch.Tensor:

@@ -16,8 +16,10 @@ end in the vocabulary projection (``acehip_lm_head_bf16``).  The batch is ``[con
 left-padded to a common length (``:894-910``); RoPE positions are cache indices, padding
 included, as transformers computes them when no ``position_ids`` are passed.
 
-The FSM-constrained processor, repetition penalty, top-k / top-p, temperature and the
-multinomial stay in torch, where the reference has them.  ``generate()`` (no CFG, no
+The FSM-constrained processor, repetition penalty, temperature and the multinomial stay in
+torch, where the reference has them; so do top-k / top-p (``_apply_top_k_filter`` /
+``_apply_top_p_filter``, ``:367-385``) unless ``install_lm(..., filters=True)`` rebinds them to
+:class:`HipLogitFilters` (``acehip_lm_filter``).  ``generate()`` (no CFG, no
 constrained decoding, ``:946``) and scoring (``core/scoring/lm_score.py`` needs logits at
 every position) stay on the wrapped module.
 
@@ -284,3 +286,69 @@ class HipCausalLM:
         close = getattr(self.rt, "close", None)
         if close:
             close()
+
+
+class HipLogitFilters:
+    """``LLMHandler._apply_top_k_filter`` / ``_apply_top_p_filter`` (``acestep/llm_inference.py:367-385``)
+    on ``acehip_lm_filter``: the same signatures, the logits filtered in place and the same tensor
+    object returned, each method with the other filter off.
+
+    A method calls the original it was built with — never the kernel — when its filter is
+    switched off (top_k ``None`` / ``<= 0``; top_p ``None`` or outside (0, 1)) or when ``logits``
+    is not a 2-D CUDA tensor of unit inner stride and dtype float32 or bfloat16 (the MLX bridge's
+    CPU tensors, ``:3646-3647``).  ``fallback``: an acehip error in a call is logged and that call
+    runs on the original.  The workspace is per device, allocated on first use and kept."""
+
+    def __init__(self, orig_top_k, orig_top_p, fallback: bool = False, max_batch: int = 16, vocab: int = 1 << 18):
+        self.orig_top_k, self.orig_top_p = orig_top_k, orig_top_p
+        self.fallback = fallback
+        self.max_batch, self.vocab = max_batch, vocab
+        self._ws: Dict[torch.device, torch.Tensor] = {}
+
+    @staticmethod
+    def eligible(logits) -> bool:
+        return (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dim() == 2 and logits.numel() > 0
+                and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]
+                and logits.dtype in (torch.float32, torch.bfloat16))
+
+    def _workspace(self, logits: torch.Tensor) -> torch.Tensor:
+        B, V = logits.shape
+        need = int(lib().acehip_lm_filter_ws_bytes(B, V))
+        ws = self._ws.get(logits.device)
+        if ws is None or ws.numel() < need:
+            need = max(need, int(lib().acehip_lm_filter_ws_bytes(max(B, self.max_batch), max(V, self.vocab))))
+            ws = torch.empty(need, dtype=torch.uint8, device=logits.device)
+            self._ws[logits.device] = ws
+        return ws
+
+    def _run(self, logits: torch.Tensor, top_k: int, top_p: float) -> torch.Tensor:
+        B, V = logits.shape
+        ws = self._workspace(logits)
+        with torch.cuda.device(logits.device):
+            check(lib().acehip_lm_filter(ptr(logits), _ffi.dtype_code(logits), logits.stride(0), B, V, top_k, top_p,
+                                         ptr(ws), ws.numel(), stream_ptr()), "lm_filter")
+        return logits
+
+    def top_k(self, logits, top_k):
+        if top_k is None or top_k <= 0 or not self.eligible(logits):
+            return self.orig_top_k(logits, top_k)
+        if top_k >= logits.shape[1]:          # torch.topk's own error for k > V; k == V removes nothing
+            return self.orig_top_k(logits, top_k)
+        try:
+            return self._run(logits, int(top_k), 0.0)
+        except RuntimeError as e:
+            if not self.fallback:
+                raise
+            log.warning("acehip top-k filter failed (%s); this call runs on PyTorch", e)
+            return self.orig_top_k(logits, top_k)
+
+    def top_p(self, logits, top_p):
+        if top_p is None or not 0.0 < top_p < 1.0 or not self.eligible(logits):
+            return self.orig_top_p(logits, top_p)
+        try:
+            return self._run(logits, 0, float(top_p))
+        except RuntimeError as e:
+            if not self.fallback:
+                raise
+            log.warning("acehip top-p filter failed (%s); this call runs on PyTorch", e)
+            return self.orig_top_p(logits, top_p)

@@ -220,6 +220,11 @@ int attention_decode(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *
                      hipStream_t s);
 // y[m][n] = bf16(Σ_k x[m][k]·W[n][k]), M ≤ 16, any N (the LM's vocabulary projection)
 int lm_head(const bf16_t *x, int64_t ldx, const bf16_t *W, bf16_t *y, int64_t ldy, int M, int N, int K, hipStream_t s);
+// top-k / top-p logit filters of the token loop, in place (lm_filter.hip): logits [B][ld] of V
+// fp32 or bf16 (dtype ACEHIP_F32 / ACEHIP_BF16) values; ws: lm_filter_ws_bytes(B, V) bytes
+size_t lm_filter_ws_bytes(int B, int V);
+int lm_filter(void *logits, int dtype, int ld, int B, int V, int top_k, float top_p, void *ws, size_t ws_bytes,
+              hipStream_t s);
 
 // --------------------------------------------------------------- sampler ---
 // element type bf16 (f32 = false) or fp32 (the parity mode)

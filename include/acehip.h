@@ -515,6 +515,26 @@ int acehip_attention_decode_bf16(const void *q, const void *k, const void *v, vo
  * ldx % 8 == 0. */
 int acehip_lm_head_bf16(const void *x, int ldx, const void *W, void *y, int ldy, int M, int N, int K, void *stream);
 
+/* Top-k / top-p logit filters of the token loop, in place:
+ * LLMHandler._apply_top_k_filter (acestep/llm_inference.py:367-372) and
+ * LLMHandler._apply_top_p_filter (:374-385), without a sort.  logits: B rows of V values,
+ * row stride ld >= V elements, dtype ACEHIP_F32 or ACEHIP_BF16; an entry keeps its bits or
+ * becomes -inf of that dtype; columns [V, ld) are never written; -inf entries stay -inf.
+ *   top_k in [1, V): entries below the k-th largest value (duplicates counted) are removed,
+ *     ties at it are all kept; top_k <= 0 or >= V: off.
+ *   top_p in (0, 1): with p = softmax(row) in fp32 and the entries ranked by value, descending
+ *     (equal values: lower index first), rank 0 is kept and rank i >= 1 is kept iff the p of
+ *     ranks < i sums to <= top_p; otherwise off.  The mass is a fixed-point integer sum: the
+ *     same input gives the same bits on every call.
+ * Both on: top-k, then top-p over the survivors (two calls).  A row with no finite entry is
+ * left as it is.  NaN / +inf inputs are outside the contract (no fault, result unspecified).
+ * ws: device scratch of acehip_lm_filter_ws_bytes(B, V) bytes, 8-byte aligned.  Caller's
+ * stream, no allocation, no host sync.  ACEHIP_E_ARG (nothing launched): null pointer,
+ * B < 1, V < 1 or V > 2^23, ld < V, another dtype, a smaller workspace. */
+size_t acehip_lm_filter_ws_bytes(int B, int V);
+int acehip_lm_filter(void *logits, int dtype, int ld, int B, int V, int top_k, float top_p, void *ws, size_t ws_bytes,
+                     void *stream);
+
 /* Qwen3RMSNorm (+ AdaLN modulation when shift/scale are given) over rows of D
  * (transformers modeling_qwen3.py:59-64; reference base:499,530,1496):
  * out = bf16(bf16(bf16(w·bf16(x·rsqrt(mean x²+eps)))·bf16(1+scale[b])) + shift[b]),
