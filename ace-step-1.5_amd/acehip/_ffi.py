@@ -39,7 +39,7 @@ EXPORTS = [
     "acehip_enc_kv_create", "acehip_enc_prefill", "acehip_enc_decode",
     "acehip_attention_decode_ws_bytes", "acehip_attention_decode_bf16", "acehip_lm_head_bf16",
     "acehip_lm_filter_ws_bytes", "acehip_lm_filter",
-    "acehip_diag_pp_src_check",
+    "acehip_diag_pp_src_check", "acehip_diag_gemm_plan",
 ]
 
 
@@ -69,6 +69,16 @@ class AttnCapture(ctypes.Structure):
     """acehip_attn_capture (include/acehip.h)."""
     _fields_ = [("n", c_int), ("layer", POINTER(c_int)), ("head", POINTER(c_int)), ("k0", c_int), ("k1", c_int),
                 ("out", POINTER(c_float)), ("stop_after_last", c_int)]
+
+
+# acehip_gemm_plan.route (include/acehip.h ACEHIP_ROUTE_*)
+ROUTE_TILE, ROUTE_SPLITK, ROUTE_STAGED, ROUTE_TAIL2, ROUTE_TAIL1, ROUTE_WALK = range(6)
+
+
+class GemmPlan(ctypes.Structure):
+    """acehip_gemm_plan (include/acehip.h)."""
+    _fields_ = [(n, c_int) for n in ("route", "v_head", "v_tail", "M1", "nmain", "ntail", "grid", "splits", "kper",
+                                     "bn", "stages", "deferred", "saddr", "helpers")]
 
 
 _LIB = None
@@ -120,6 +130,8 @@ def _declare(lib):
         "acehip_diag_pp_src_check": (c_int64, [c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int,
                                                POINTER(c_int), POINTER(c_int64), POINTER(c_int64),
                                                POINTER(c_int64)]),
+        "acehip_diag_gemm_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int, ctypes.c_size_t, c_int, c_int,
+                                          POINTER(GemmPlan)]),
         "acehip_gemm_res_norm_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int64, c_int, c_int,
                                               P, P, P, c_int64, P, c_int, c_float, P, c_int, POINTER(c_int), P]),
         "acehip_attention_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -227,6 +239,16 @@ def _mismatch_cause(built: str) -> str:
 def missing_exports():
     l = lib()
     return [n for n in EXPORTS if not hasattr(l, n)]
+
+
+def gemm_plan(M, N, K, epi, lda=None, ldw=None, ws_bytes=48 << 20, defer_ok=False, device_cus=0) -> dict:
+    """The route the production GEMM dispatch takes for a shape under the current ACEHIP_* switches
+    (acehip_diag_gemm_plan; host only), as a dict of acehip_gemm_plan's fields.  device_cus 0: the
+    current device's; ws_bytes defaults to the runtimes' split-K workspace."""
+    out = GemmPlan()
+    check(lib().acehip_diag_gemm_plan(M, N, K, K if lda is None else lda, K if ldw is None else ldw, epi, ws_bytes,
+                                      int(defer_ok), device_cus, ctypes.byref(out)), "diag_gemm_plan")
+    return {n: getattr(out, n) for n, _ in GemmPlan._fields_}
 
 
 def reload_knobs():

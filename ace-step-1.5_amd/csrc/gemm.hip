@@ -1002,7 +1002,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
 // Persistent tile walk (SwiGLU gate/up, whose epilogue writes straight from registers and leaves
 // the operand ring alone): one workgroup per CU, workgroup w takes tiles w, w + G, w + 2G, … of
 // the launch's tile list — the main grid's 256² tiles, then the tail-split tail's 128×256 ones
-// (gemm_tail_split), i.e. the order in which the hardware hands the fused main + tail grid's
+// (gemm_plan.h plan_tail_split), i.e. the order in which the hardware hands the fused main + tail grid's
 // blocks to the CUs, so xcd_remap + GROUP_M keep their per-XCD panel sharing.  At a tile
 // boundary the ring is idle (every wave's LDS reads retired before the K loop's closing
 // barrier), so the NEXT tile's whole prologue — B(0), A(0), B(1) — is issued before this tile's
@@ -1081,7 +1081,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
     gemm_pp_body<BM, EPI, SADDR>(a, lds, blockIdx.x);
 }
 
-// The tail-split GEMM (gemm_tail_split: whole rounds of 256-row tiles + the remaining rows as
+// The tail-split GEMM (gemm_plan.h plan_tail_split: whole rounds of 256-row tiles + the remaining rows as
 // one round of 128-row tiles) in ONE launch: blocks [0, nmain) run the main grid, the rest the
 // tail grid, so the tail's blocks start on CUs as the main grid's last round drains instead of
 // behind a kernel boundary
@@ -1355,15 +1355,6 @@ int launch_w4(const GemmArgs &a, hipStream_t s) {
     return 0;
 }
 
-// Whether a one-tile ping-pong launch of BM-row tiles takes the scalar-base K loop
-// (gemm_pp_body SADDR): ACEHIP_GEMM_SADDR, and leading dimensions whose 32-bit lane offsets
-// cannot wrap — anything else keeps the pointer form, so no call that works there fails here.
-// The store / residual / SwiGLU epilogues and the fused main + tail launch (head-post included)
-// take it; the conv epilogue and the one-launch head-post grid (layer 0's deduplicated QKV) stay
-// on the pointer form — in the round-8 A/B they were ahead with it, but not by twice the
-// same-vs-same spread in every round, so they have no scalar-base instantiation.
-static bool pp_use_saddr(const GemmArgs &a, int BM) { return knobs().gemm_saddr && pp_saddr_fits(BM, a.lda, a.ldw); }
-
 template <int BM, bool SADDR>
 int launch_pp_as(const GemmArgs &a, hipStream_t s) {
     if (a.N % 256) return fail(-1, "gemm: N not a multiple of 256");
@@ -1392,7 +1383,7 @@ int launch_pp_as(const GemmArgs &a, hipStream_t s) {
 }
 template <int BM>
 int launch_pp(const GemmArgs &a, hipStream_t s) {
-    return pp_use_saddr(a, BM) ? launch_pp_as<BM, true>(a, s) : launch_pp_as<BM, false>(a, s);
+    return pp_tile_saddr(knobs().gemm_saddr, a.epi, BM, a.lda, a.ldw) ? launch_pp_as<BM, true>(a, s) : launch_pp_as<BM, false>(a, s);
 }
 
 template <int BM, int BN, int WM, int WN, int STAGES, int NH = 0>
@@ -1452,105 +1443,14 @@ bool gemm_ext_events(hipEvent_t start, hipEvent_t stop) {
     return consumed;
 }
 
-// the CU count the tile planner (gemm_pick_variant, gemm_tail_split, the persistent grid) fills:
-// the device's, or fewer under ACEHIP_GEMM_CUS so tests reach multi-round grids at small shapes
-static int plan_cus() {
-    const int cap = knobs().gemm_cus, n = device_cus();
-    return cap > 0 && cap < n ? cap : n;
-}
-
-// The persistent SwiGLU tile walk (gemm_pp_persist_kernel): the main grid's nmain 256² tiles
-// and the tail's ntail 128×256 ones (at most one per workgroup) on one workgroup per planned CU
-static int launch_pp_persist(const GemmArgs &hd, const GemmArgs &tl, int nmain, int ntail, hipStream_t s) {
-    const int grid = std::min(plan_cus(), nmain + ntail);
-    if (ntail > grid) return fail(-1, "gemm: persistent walk with more tail tiles than workgroups");
-    klaunch(gemm_pp_persist_kernel<EPI_SWIGLU>, dim3(grid), dim3(512), s, hd, tl, nmain, nmain + ntail);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Half-chip grids (M ≈ 3000: the conditional rows' cross-Q / cross-O): the four-wave
-// 192×128 tile with a 3-deep ring fills the chip in one round (16 × 16 tiles at
-// N = 2048) where the 128² tile runs 0.75 of a 2-blocks-per-CU round: 34–35 → 31 µs,
-// hot or cold weights (tools/bench_gemm.py, r02).
-static bool use_w4s(int64_t M, int N) {
-    if (N % 128) return false;
-    const int cus = device_cus();
-    const int64_t t = ((M + 191) / 192) * (N / 128);
-    return t <= cus && t * 4 >= (int64_t)cus * 3;
-}
-
-// Tile choice from a one-block-per-CU cost model fitted on MI355X
-// (tools/bench_gemm.py): time ∝ ⌈tiles / CUs⌉ × per-tile time, with a 256×256
-// ping-pong tile costing 1.093× a 192×256 one (it does 1.33× the work).  The
-// model reproduces the measured v7/v8 ratios on all four DiT shapes to 2 %.
-// Grids that fill at most half the chip fall back to 128×128 (2 blocks/CU): at
-// M = 3000, N = 2048 (the cross-O GEMM of the conditional rows) 37 µs vs 46 µs.
-int gemm_pick_variant(int64_t M, int N) {
-    if (use_w4s(M, N) && (N % 256 || ((M + 191) / 192) * (N / 256) <= device_cus() / 2)) return 13;
-    if (N % 256) return 0;
-    const int cus = plan_cus();
-    const int64_t t7 = ((M + 255) / 256) * (N / 256), t8 = ((M + 191) / 192) * (N / 256);
-    if (t8 <= cus / 2) return 0;
-    // one partial round of 192-row tiles (M ≈ 500: the 20 s song's CFG batch, the lyric
-    // encoder's SwiGLU): 128-row tiles still fit one round and finish sooner
-    const int64_t t9 = ((M + 127) / 128) * (N / 256);
-    if (t8 <= cus && t9 <= cus) return 9;
-    const double c7 = (double)((t7 + cus - 1) / cus) * 1.093, c8 = (double)((t8 + cus - 1) / cus);
-    return c7 < c8 ? 7 : 8;
-}
-
-// Split-K for grids that cannot fill half the chip even with 128×128 tiles (short
-// songs / turbo: M = Bc·S of a few hundred rows): the K range is split so the grid
-// reaches ~1 block per CU (at least 4 K-tiles per split), every split stores fp32
-// partials, and the epilogue is either folded into the consumer (head_post for the
-// head-post case; the next rmsnorm_mod for residual epilogues, gemm(…, defer)) or run
-// by splitk_epilogue_kernel.  Ring depth (tools/ab_splitk.py, M = 125): 3 stages for
-// N ≤ 4096 (down / QKV / O: 20.1 → 19.0, 18.3 → 17.4, 15.1 → 14.9 µs), 2 for the wide
-// SwiGLU (26.2 vs 28.3 µs).
-static int splitk_finish(const GemmArgs &a, const GemmArgs &p, int splits, hipStream_t s);
-
-// split-K tile width: 64-column tiles double the grid at a given split count (half the splits
-// and partial bytes for ~1 block per CU).  Round 3 kept 128 where N and K < 4096 (O at M = 125
-// measured 18.7 → 25.3 µs on 64); round 4 measured every shape faster on 64 (O 16.0 → 14.7, QKV
-// 15.4 → 14.8, `profiles/r04h2_small_m.log`) and the songs too (turbo 10 s DiT 25.6 → 24.6 ms,
-// base 10 s 96.9 → 93.9, `profiles/r04h3_ab_turbo.log`): 64 everywhere.  ACEHIP_SPLITK_BN =
-// 128 | 64 forces one (A/B)
-static int splitk_bn(const GemmArgs &) {
-    const int f = knobs().splitk_bn;
-    if (f) return f == 64 ? 64 : 128;
-    return 64;
-}
-static void fill_defer(const GemmArgs &a, int splits, RowAdd *defer);
-static int gemm_splitk(const GemmArgs &a, int splits, hipStream_t s, RowAdd *defer = nullptr) {
-    GemmArgs p = a;
-    const int nk = a.K / BK;
-    p.kper = (nk + splits - 1) / splits;
-    splits = (nk + p.kper - 1) / p.kper;
-    const int bn = splitk_bn(a);
-    const int tiles = ((a.M + 127) / 128) * (a.N / bn);
-    // (helper waves measured no gain here: 2 MFMA waves / SIMD already cover the DMA issue)
-    if (bn == 64) gemm_kernel<128, 64, 4, 1, 3, EPI_PARTIAL><<<dim3(tiles, splits), 256, 0, s>>>(p);
-    else if (a.N <= 4096) gemm_kernel<128, 128, 2, 2, 3, EPI_PARTIAL><<<dim3(tiles, splits), 256, 0, s>>>(p);
-    else gemm_kernel<128, 128, 2, 2, 2, EPI_PARTIAL><<<dim3(tiles, splits), 256, 0, s>>>(p);
-    HIP_TRY(hipGetLastError());
-    if (defer) {
-        fill_defer(a, splits, defer);
-        return 0;
-    }
-    return splitk_finish(a, p, splits, s);
-}
-
-// the residual epilogue is left to the consumer norm (in place: C == res)
-static void fill_defer(const GemmArgs &a, int splits, RowAdd *defer) {
-    defer->xw = a.C;
-    defer->part = (const float *)a.ws;
-    defer->splits = splits;
-    defer->prows = a.M;
-    defer->plane = (int64_t)a.M * a.N;
-    defer->gate = a.epi == EPI_GATED_RES ? a.gate : nullptr;
-    defer->gate_bstride = a.gate_bstride;
-    defer->gate_rpb = a.epi == EPI_GATED_RES ? a.rows_per_batch : 1;
+// what gemm_plan reads besides the shape: the device's CU count, the count the tile planner
+// fills (fewer under ACEHIP_GEMM_CUS, so tests reach multi-round grids at small shapes; PlanEnv
+// says which decision reads which) and the planner's A/B switches
+static PlanEnv plan_env(int dev_cus = 0) {
+    const Knobs &k = knobs();
+    const int n = dev_cus > 0 ? dev_cus : device_cus();
+    return {n, k.gemm_cus > 0 && k.gemm_cus < n ? k.gemm_cus : n, k.gemm_tailsplit, k.gemm_helpers, k.splitk_fuse,
+            k.splitk_bn, k.smallm_wholek, k.gemm_hp_tail, k.gemm_persist, k.gemm_saddr};
 }
 
 // sum the fp32 split partials in order + the GEMM's epilogue (head-post: staged bf16
@@ -1584,61 +1484,73 @@ static int splitk_finish(const GemmArgs &a, const GemmArgs &p, int splits, hipSt
     return 0;
 }
 
-// Tail split for ping-pong grids whose last round is a small fraction of the chip
-// (SwiGLU gate/up at 240 s: 24 × 48 = 1152 tiles of 256² on 256 CUs = 4.5 rounds, the
-// last half-round costing a whole tile time): rows [0, M1) keep the big tile with
-// M1 chosen so their grid is whole rounds (less at most one row of tiles), and the
-// remaining rows run as one round of 128×256 two-phase ping-pong tiles where they fit one
-// round (variant 9), else of 128×128 tiles (2 blocks/CU, variant 0).  Row-local epilogues
-// only: store, SwiGLU and head-post (whose tail needs the 128×256 tile: the 128×128 one has
-// no head-post epilogue); the gated residual indexes its batch by row.
-// ACEHIP_GEMM_TAILSPLIT=0 disables it.  Returns 1 when not applicable.
-static int gemm_tail_split(const GemmArgs &a, int v, hipStream_t s) {
-    if (a.epi != EPI_SWIGLU && a.epi != EPI_STORE && a.epi != EPI_HEADPOST) return 1;
-    if (!knobs().gemm_tailsplit) return 1;
-    const int BMv = v == 7 ? 256 : 192, cus = plan_cus();   // v = 7 or 8
-    const int64_t nN = a.N / 256, tiles = (int64_t)((a.M + BMv - 1) / BMv) * nN;
-    const int64_t full = tiles / cus, rem = tiles - full * cus;
-    if (full < 1 || rem == 0 || rem * 5 > (int64_t)cus * 3) return 1;   // last round > 60 % full
-    const int64_t M1 = (full * cus / nN) * BMv;
-    if (M1 <= 0 || M1 >= a.M) return 1;
-    if (((a.M - M1 + 127) / 128) * (a.N / 128) > 2 * (int64_t)cus) return 1;
-    GemmArgs hd = a;
-    hd.M = (int)M1;
-    GemmArgs tl = a;
-    tl.M = a.M - (int)M1;
-    tl.A = a.A + M1 * a.lda;
-    if (a.epi == EPI_HEADPOST) tl.hp.m_off += (int)M1;   // C unused: rows scatter by (b, s)
-    else tl.C = a.C + M1 * a.ldc;
-    // the tail as one round of 128×256 two-phase ping-pong tiles
-    const bool pp128 = a.N % 256 == 0 && ((tl.M + 127) / 128) * nN <= cus;
-    if (a.epi == EPI_HEADPOST && !pp128) return 1;   // the 128×128 tail tile has no head-post epilogue
-    if (pp128 && v == 7) {
-        // both grids in one launch (the main grid's block count is a multiple of 8, so the tail
-        // blocks' XCD is their own index mod 8, as in a launch of their own)
-        const int nmain = (int)(full * cus / nN * nN), ntail = ((tl.M + 127) / 128) * (int)nN;
-        // SwiGLU: one persistent walk over both grids (ACEHIP_GEMM_PERSIST=0: the launch below)
-        if (a.epi == EPI_SWIGLU && knobs().gemm_persist && pp_saddr_fits(256, a.lda, a.ldw) &&
-            nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0)
-            return launch_pp_persist(hd, tl, nmain, ntail, s);
-        if (nmain % 8 == 0 && nmain == (hd.M / 256) * (int)nN && hd.M % 256 == 0) {
-            const dim3 grid(nmain + ntail), block(512);
-            if (pp_use_saddr(a, 256)) {   // head and tail share lda / ldw; 256 rows bound both tiles
-                if (a.epi == EPI_SWIGLU) klaunch(gemm_pp_split_kernel<EPI_SWIGLU, true>, grid, block, s, hd, tl, nmain);
-                else if (a.epi == EPI_HEADPOST) gemm_pp_split_kernel<EPI_HEADPOST, true><<<grid, block, 0, s>>>(hd, tl, nmain);
-                else gemm_pp_split_kernel<EPI_STORE, true><<<grid, block, 0, s>>>(hd, tl, nmain);
-            } else {
-                if (a.epi == EPI_SWIGLU) klaunch(gemm_pp_split_kernel<EPI_SWIGLU, false>, grid, block, s, hd, tl, nmain);
-                else if (a.epi == EPI_HEADPOST) gemm_pp_split_kernel<EPI_HEADPOST, false><<<grid, block, 0, s>>>(hd, tl, nmain);
-                else gemm_pp_split_kernel<EPI_STORE, false><<<grid, block, 0, s>>>(hd, tl, nmain);
-            }
+// The launches of a plan (gemm_plan.h), in order.  Tail splits and the walk with a tail run rows
+// [0, M1) as hd and rows [M1, M) as tl.
+static int gemm_launch(const GemmArgs &a, const GemmPlan &p, hipStream_t s, RowAdd *defer) {
+    using Kern1 = void (*)(GemmArgs);
+    using Kern2 = void (*)(GemmArgs, GemmArgs, int);
+    GemmArgs hd = a, tl = a;
+    if (p.ntail) {
+        hd.M = p.M1;
+        tl.M = a.M - p.M1;
+        tl.A = a.A + (int64_t)p.M1 * a.lda;
+        if (a.epi == EPI_HEADPOST) tl.hp.m_off += p.M1;   // C unused: rows scatter by (b, s)
+        else tl.C = a.C + (int64_t)p.M1 * a.ldc;
+    }
+    switch (p.route) {
+        case ACEHIP_ROUTE_TILE: return gemm_variant(a, p.v_head, s);
+        case ACEHIP_ROUTE_TAIL2:
+            if (int rc = gemm_variant(hd, p.v_head, s)) return rc;
+            return gemm_variant(tl, p.v_tail, s);
+        case ACEHIP_ROUTE_STAGED: {   // the projection as bf16 [M][N] in the workspace, then head_post
+            GemmArgs st = a;
+            st.epi = EPI_STORE;
+            st.bias = nullptr;
+            st.C = (bf16_t *)a.ws;
+            st.ldc = a.N;
+            if (int rc = gemm_variant(st, p.v_head, s)) return rc;
+            HeadPostArgs hh = a.hp;
+            hh.src = st.C;
+            hh.ld_src = a.N;
+            return head_post(hh, s);
+        }
+        case ACEHIP_ROUTE_WALK:   // gemm_pp_persist_kernel: at most one tail tile per workgroup
+            if (p.ntail > p.grid) return fail(-1, "gemm: persistent walk with more tail tiles than workgroups");
+            klaunch(gemm_pp_persist_kernel<EPI_SWIGLU>, dim3(p.grid), dim3(512), s, hd, tl, p.nmain, p.nmain + p.ntail);
+            break;
+        case ACEHIP_ROUTE_SPLITK: {   // fp32 partials of p.splits K ranges, then their sum + the epilogue
+            GemmArgs q = a;
+            q.kper = p.kper;
+            const Kern1 k = p.bn == 64      ? (Kern1)gemm_kernel<128, 64, 4, 1, 3, EPI_PARTIAL>
+                            : p.stages == 3 ? (Kern1)gemm_kernel<128, 128, 2, 2, 3, EPI_PARTIAL>
+                                            : (Kern1)gemm_kernel<128, 128, 2, 2, 2, EPI_PARTIAL>;
+            k<<<dim3(p.grid, p.splits), 256, 0, s>>>(q);
             HIP_TRY(hipGetLastError());
+            if (!p.deferred) return splitk_finish(a, q, p.splits, s);
+            // the residual epilogue is left to the consumer norm (in place: C == res)
+            defer->xw = a.C;
+            defer->part = (const float *)a.ws;
+            defer->splits = p.splits;
+            defer->prows = a.M;
+            defer->plane = (int64_t)a.M * a.N;
+            defer->gate = a.epi == EPI_GATED_RES ? a.gate : nullptr;
+            defer->gate_bstride = a.gate_bstride;
+            defer->gate_rpb = a.epi == EPI_GATED_RES ? a.rows_per_batch : 1;
             return 0;
         }
+        case ACEHIP_ROUTE_TAIL1: {   // gemm_pp_split_kernel by source-address form and epilogue
+            static const Kern2 split[2][3] = {
+                {gemm_pp_split_kernel<EPI_SWIGLU, true>, gemm_pp_split_kernel<EPI_HEADPOST, true>, gemm_pp_split_kernel<EPI_STORE, true>},
+                {gemm_pp_split_kernel<EPI_SWIGLU, false>, gemm_pp_split_kernel<EPI_HEADPOST, false>, gemm_pp_split_kernel<EPI_STORE, false>}};
+            const Kern2 k = split[p.saddr ? 0 : 1][a.epi == EPI_SWIGLU ? 0 : a.epi == EPI_HEADPOST ? 1 : 2];
+            if (a.epi == EPI_SWIGLU) klaunch(k, dim3(p.grid), dim3(512), s, hd, tl, p.nmain);
+            else k<<<p.grid, 512, 0, s>>>(hd, tl, p.nmain);
+            break;
+        }
+        default: return fail(-1, "gemm: bad route");
     }
-    int rc = gemm_variant(hd, v, s);
-    if (rc) return rc;
-    return gemm_variant(tl, pp128 ? 9 : 0, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // the conv epilogue on 64-row ping-pong tiles
@@ -1658,20 +1570,15 @@ int gemm_conv(const GemmArgs &a, hipStream_t s) {
     if (a.res && (a.N != a.conv_cout || a.ldr != a.N || a.conv_ostride != 1 || a.conv_ooff != 0 || a.conv_lout != a.M))
         return fail(-1, "gemm_conv: a residual needs one phase with output row = m");
     if ((int64_t)((a.M + 255) / 256) * (a.N / 256) >= (1ll << 31)) return fail(-1, "gemm_conv: grid too large");
-    // short activations (a 10 s decode's C = 1024 / 512 blocks: 40 / 118 tiles of 256 rows on
-    // 256 CUs): 128-row tiles double the grid, 64-row tiles (80 KB of LDS, 118 VGPRs: two blocks
-    // per CU) quadruple it.  10 s decode 2.13 → 1.96 (128) → 1.91 ms (64 below a quarter of the
-    // chip), bit-identical (profiles/r05az_ab_vae_small_tiles.log)
-    const int64_t t256 = (int64_t)((a.M + 255) / 256) * (a.N / 256);
-    if (t256 * 4 <= device_cus()) return launch_conv64(a, s);
-    if (t256 * 2 <= device_cus()) return launch_pp<128>(a, s);
-    return launch_pp<256>(a, s);
+    switch (conv_tile_rows(a.M, a.N, device_cus())) {
+        case 64: return launch_conv64(a, s);
+        case 128: return launch_pp<128>(a, s);
+        default: return launch_pp<256>(a, s);
+    }
 }
 
-int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
-    if (defer) defer->part = nullptr;
-    if (a.M <= 0) return 0;
-    // argument checks shared by every path (split-K included)
+// what every path (split-K included) needs of a GEMM's shape and epilogue arguments
+static int gemm_check(const GemmArgs &a) {
     if (a.N % 128 || a.K % BK || a.K <= 0)
         return fail(-1, "gemm: N%128 / K%64 violated (M=" + std::to_string(a.M) + " N=" +
                             std::to_string(a.N) + " K=" + std::to_string(a.K) + ")");
@@ -1684,71 +1591,17 @@ int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
             h.S_dst < h.S || (h.S_dst_q && h.S_dst_q < h.S) || (h.nq && !h.qw) || (h.nk && !h.kw) || (h.cos == nullptr) != (h.sin == nullptr))
             return fail(-1, "gemm: head-post arguments inconsistent with the GEMM shape");
     }
-    const Knobs &kn = knobs();
+    return 0;
+}
+
+int gemm(const GemmArgs &a, hipStream_t s, RowAdd *defer) {
+    if (defer) defer->part = nullptr;
+    if (a.M <= 0) return 0;
+    if (int rc = gemm_check(a)) return rc;
     // a deferred epilogue needs the in-place residual form the consumer norm applies
-    const bool dfr = defer && kn.splitk_fuse && (a.epi == EPI_GATED_RES || a.epi == EPI_RES) && a.res == a.C &&
-                     a.ldr == a.ldc && a.ldc == a.N;
-    // SwiGLU of one 128-row chunk (turbo / short songs, M ≤ 128): whole-K 128×64 tiles with the
-    // SwiGLU epilogue fused (variant 16: no fp32 partials, no second launch) — M = 125, cold
-    // weights: 26.1 → 19.0 µs (tools/bench_small_m.py).  ACEHIP_SMALLM_WHOLEK=0: split-K (A/B)
-    if (a.epi == EPI_SWIGLU && a.M <= 128 && a.N % 64 == 0 && kn.smallm_wholek) return gemm_variant(a, kn.smallm_wholek == 2 ? 17 : 16, s);
-    if (a.ws && a.N % 128 == 0 && a.K % BK == 0 && (a.N % 256 == 0 || a.epi != EPI_HEADPOST)) {
-        const int cus = device_cus();
-        const int64_t tiles = ((a.M + 127) / 128) * (a.N / 128);
-        const int nk = a.K / BK;
-        if (tiles * 2 <= cus && nk >= 8) {
-            const int64_t tb = ((a.M + 127) / 128) * (a.N / splitk_bn(a));   // grid tiles of the split kernel
-            int splits = (int)std::min<int64_t>(std::min<int64_t>(16, nk / 4), (cus + tb - 1) / tb);
-            const size_t need = (size_t)splits * a.M * a.N * 4 + (size_t)a.M * a.N * 2;
-            if (splits >= 2 && need <= a.ws_bytes) return gemm_splitk(a, splits, s, dfr ? defer : nullptr);
-        }
-    }
-    if (a.epi == EPI_HEADPOST) {
-        // a 192×256 grid that fills at most half the chip (cross-Q of the conditional rows,
-        // M = 3000) runs as 192×128 tiles — one head each — with the same fused epilogue; a
-        // small grid outside the four-wave tile's geometry goes through the staging buffer +
-        // the standalone head_post kernel on 128×128 tiles
-        const int64_t t192 = (int64_t)((a.M + 191) / 192) * (a.N / 256);
-        const bool small = t192 * 2 <= device_cus();
-        if (small && use_w4s(a.M, a.N)) return gemm_variant(a, 13, s);
-        if (small && a.ws && (size_t)a.M * a.N * 2 <= a.ws_bytes) {
-            GemmArgs st = a;
-            st.epi = EPI_STORE;
-            st.bias = nullptr;
-            st.C = (bf16_t *)a.ws;
-            st.ldc = a.N;
-            int rc = gemm_variant(st, 0, s);
-            if (rc) return rc;
-            HeadPostArgs hh = a.hp;
-            hh.src = st.C;
-            hh.ld_src = a.N;
-            return head_post(hh, s);
-        }
-        // whole rounds of 256-row tiles + one round of 128-row tiles where that costs less than
-        // the 192-row rounds (cost model of gemm_pick_variant, a 128×256 tile ≈ 0.6 of a 192×256
-        // one): QKV at 240 s, 32 × 16 = 2 rounds of 192 → 1 round of 256 + 1 of 128
-        if (kn.gemm_hp_tail && a.N % 256 == 0) {
-            const int cus = device_cus();
-            const int64_t nN = a.N / 256, t7 = ((a.M + 255) / 256) * nN, t8 = ((a.M + 191) / 192) * nN;
-            const double c_split = (double)(t7 / cus) * 1.093 + 0.6, c8 = (double)((t8 + cus - 1) / cus);
-            if (t7 >= cus && c_split < c8) {
-                const int rc = gemm_tail_split(a, 7, s);
-                if (rc <= 0) return rc;
-            }
-        }
-        return gemm_variant(a, 8, s);
-    }
-    const int v = gemm_pick_variant(a.M, a.N);
-    if (v == 7 || v == 8) {
-        const int rc = gemm_tail_split(a, v, s);
-        if (rc <= 0) return rc;   // split done (0) or failed (< 0); 1 = not applicable
-    }
-    // a multi-round SwiGLU grid of 256² tiles without a tail split: the same persistent walk
-    if (v == 7 && a.epi == EPI_SWIGLU && knobs().gemm_persist && pp_saddr_fits(256, a.lda, a.ldw)) {
-        const int64_t tiles = (int64_t)((a.M + 255) / 256) * (a.N / 256);
-        if (tiles > plan_cus() && tiles < (1ll << 30)) return launch_pp_persist(a, a, (int)tiles, 0, s);
-    }
-    return gemm_variant(a, v, s);
+    const bool defer_ok = defer && a.res == a.C && a.ldr == a.ldc && a.ldc == a.N;
+    const PlanIn in{a.M, a.N, a.K, a.epi, a.lda, a.ldw, a.ws ? a.ws_bytes : 0, defer_ok};
+    return gemm_launch(a, gemm_plan(in, plan_env()), s, defer);
 }
 
 // ---------------------------------------------------------------------------
@@ -1762,17 +1615,10 @@ bool cross_fuse_shape(const GemmArgs &cq, int KV, int Sk) {
            h.nv == 0 && !h.cos && !h.sin && h.qw && h.m_off == 0 && h.S > 0 && (int64_t)h.B * h.S == cq.M &&
            KV > 0 && h.nq == 2 * KV && Sk > 0 && (h.B == 1 || h.S % 192 == 0) && (cq.lda | cq.ldw) % 8 == 0;
 }
-// cross_fuse_planned: gemm() runs cq on the half-chip four-wave tile with its helper waves
-// (variant 13: one round of 192 × 128 tiles on at least three quarters of the planned CUs, and
-// not the small-M split-K path); the CU count is the planner's (ACEHIP_GEMM_CUS in tests)
-bool cross_fuse_planned(const GemmArgs &cq) {
-    if (!knobs().gemm_helpers || cq.N % 256) return false;
-    const int cus = plan_cus();
-    const int64_t t = (int64_t)((cq.M + 191) / 192) * (cq.N / 128);
-    const int64_t t128 = (int64_t)((cq.M + 127) / 128) * (cq.N / 128);
-    if (cq.ws && t128 * 2 <= cus && cq.K / BK >= 8) return false;   // split-K
-    return t <= cus && t * 4 >= (int64_t)cus * 3;
-}
+// cross_fuse_planned: cq belongs on the half-chip four-wave tile with its helper waves (variant
+// 13: one round of 192 × 128 tiles on at least three quarters of the planned CUs, and not the
+// small-M split-K path) — gemm_plan.h cross_fuse_plan, which says how it differs from gemm()'s route
+bool cross_fuse_planned(const GemmArgs &cq) { return cross_fuse_plan(cq.M, cq.N, cq.K, cq.ws != nullptr, plan_env()); }
 int cross_q_attention(const GemmArgs &cq, const bf16_t *k, const bf16_t *v, bf16_t *o, int KV, int Sk, float scale,
                       int64_t o_ld, hipStream_t s) {
     if (!cross_fuse_shape(cq, KV, Sk)) return fail(-1, "cross_q_attention: shape outside the fused kernel's");
@@ -1785,6 +1631,17 @@ int cross_q_attention(const GemmArgs &cq, const bf16_t *k, const bf16_t *v, bf16
 }
 
 }  // namespace acehip
+
+// Host-only window on the dispatch (tests; no kernel launch): the plan gemm() would launch from
+extern "C" int acehip_diag_gemm_plan(int M, int N, int K, int64_t lda, int64_t ldw, int epi, size_t ws_bytes,
+                                     int defer_ok, int device_cus, acehip_gemm_plan *out) {
+    using namespace acehip;
+    if (!out || M <= 0 || N <= 0 || N % 128 || K <= 0 || K % BK || epi < EPI_STORE || epi > EPI_HEADPOST ||
+        (epi == EPI_HEADPOST && N % 256) || lda < K || ldw < K || (lda | ldw) % 8 || device_cus < 0)
+        return fail(ACEHIP_E_ARG, "diag_gemm_plan: a shape gemm() refuses, or a null plan");
+    *out = gemm_plan(PlanIn{M, N, K, epi, lda, ldw, ws_bytes, defer_ok != 0}, plan_env(device_cus));
+    return 0;
+}
 
 // Host-only check of the two source-address forms (tests; no GPU call): for every row tile, column
 // tile, wave, lane, piece and K-tile of a BM × 256 ping-pong grid, the byte address relative to A / W

@@ -1,6 +1,7 @@
 // kernels.h — launchers for every device kernel of libacehip (internal C++ API).
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace acehip {
 
@@ -38,7 +39,7 @@ struct Knobs {
 };
 const Knobs &knobs();
 // compute units of the current device (256 if the query fails), read once per process; every
-// planner puts its own policy on top (plan_cus, num_cus_attn, decode_cus)
+// planner puts its own policy on top (gemm.hip plan_env, num_cus_attn, decode_cus)
 int device_cus();
 
 // ------------------------------------------------------------------ GEMM ---
@@ -59,15 +60,7 @@ struct HeadPostArgs {
     int S_dst_q = 0;                     // rows per head of q where they differ from k / v's S_dst (0: S_dst) —
                                          // the token loop writes k / v into a cache of `capacity` rows per head
 };
-enum GemmEpi {
-    EPI_STORE = 0,       // C = bf16(acc + bias)
-    EPI_GATED_RES = 1,   // C = bf16(res + bf16(bf16(acc) * gate[b][n]))   (AdaLN-Zero gated residual)
-    EPI_RES = 2,         // C = bf16(res + bf16(acc))                       (plain residual)
-    EPI_SWIGLU = 3,      // packed [gate|up] blocks of 32 rows → C[M, N/2] = bf16(silu(g)·u)
-    EPI_HEADPOST = 4,    // bf16(acc) staged in LDS, then per-128-column head: q/k RMSNorm (+RoPE) and
-                         // scatter to head-major [B][heads][S][128] (GemmArgs::hp); C unused
-};
-
+// (enum GemmEpi, EPI_PARTIAL and EPI_CONV: gemm_plan.h)
 
 struct GemmArgs {
     const bf16_t *A; int64_t lda;   // [M, K]
@@ -96,8 +89,6 @@ struct GemmArgs {
     int conv_cin, conv_dil, conv_a0, conv_ostride, conv_ooff, conv_cout;
     int64_t conv_lout;
 };
-constexpr int EPI_PARTIAL = 5;                       // internal: fp32 partials of split blockIdx.y → ws
-constexpr int EPI_CONV = 6;                          // the VAE's implicit-GEMM convs (gemm_conv)
 constexpr size_t GEMM_WS_BYTES = (size_t)48 << 20;   // runtimes' split-K workspace
 struct RowAdd;
 // defer != null: a residual-epilogue GEMM (EPI_GATED_RES / EPI_RES) that takes the small-M

@@ -462,6 +462,39 @@ int64_t acehip_diag_pp_src_check(int M, int N, int K, int64_t lda, int64_t ldw, 
                                  int conv_dil, int conv_a0, int *fits, int64_t *min_a, int64_t *max_a,
                                  int64_t *max_b);
 
+/* The route acehip_gemm_bf16_ex(..., variant -1) and the runtimes' GEMMs take for a shape: the
+ * value the library's dispatch plans before it launches (csrc/gemm_plan.h holds the rules).
+ * Fields a route does not use are 0. */
+enum {
+    ACEHIP_ROUTE_TILE = 0,    /* one grid of tile variant v_head (the variants of acehip_gemm_bf16_ex) */
+    ACEHIP_ROUTE_SPLITK = 1,  /* splits x kper K-tiles of fp32 partials on 128 x bn tiles, then the epilogue */
+    ACEHIP_ROUTE_STAGED = 2,  /* head-post: a 128 x 128 store grid into the workspace + the head_post kernel */
+    ACEHIP_ROUTE_TAIL2 = 3,   /* rows [0, M1) on v_head, then rows [M1, M) on v_tail: two launches */
+    ACEHIP_ROUTE_TAIL1 = 4,   /* the same split as nmain 256 x 256 + ntail 128 x 256 tiles of one launch */
+    ACEHIP_ROUTE_WALK = 5     /* SwiGLU: those nmain + ntail tiles walked by `grid` persistent workgroups */
+};
+typedef struct acehip_gemm_plan {
+    int route;
+    int v_head, v_tail;       /* tile variants (v_tail: the tail split's second grid) */
+    int M1;                   /* rows of the main grid (tail splits; the walk: M without a tail) */
+    int nmain, ntail;         /* tiles of the main and the tail grid (tail splits, walk) */
+    int grid;                 /* workgroups of the first (or only) launch; split-K: per split */
+    int splits, kper;         /* split-K: splits of kper K-tiles (the last one may be shorter) */
+    int bn, stages;           /* split-K: tile width (64 / 128) and operand ring depth */
+    int deferred;             /* split-K: the residual epilogue is left to the consumer norm */
+    int saddr;                /* the ping-pong launches issue their LDS-DMAs in the scalar-base form */
+    int helpers;              /* the tile runs with LDS-DMA helper waves */
+} acehip_gemm_plan;
+
+/* Host-only, for tests (no kernel launch): the plan of an [M, K] x [N, K]^T GEMM with epilogue
+ * epi (0 store, 1 gated residual, 2 residual, 3 SwiGLU, 4 head-post), ws_bytes of split-K
+ * workspace (0: none) and, with defer_ok, a caller that accepts a deferred residual epilogue —
+ * under the ACEHIP_* switches of the environment (ACEHIP_GEMM_CUS included) on a device of
+ * device_cus compute units (0: the current device's).  Shapes the dispatch refuses return
+ * ACEHIP_E_ARG. */
+int acehip_diag_gemm_plan(int M, int N, int K, int64_t lda, int64_t ldw, int epi, size_t ws_bytes, int defer_ok,
+                          int device_cus, acehip_gemm_plan *out);
+
 /* A residual GEMM and the norm that consumes it, as the DiT layer issues the pair (tests):
  *   X[0:M] = residual epilogue (as above, in place, N = ldc = D) of A[M,K] · W[D,K]^T
  *   X[from:M_norm] = bf16(X + v[D])                         (v != NULL; M <= from <= M_norm)

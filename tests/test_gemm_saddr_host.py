@@ -12,7 +12,7 @@ Bounds: without a conv shift the pieces stay inside their operand — A offsets 
 [0, M·lda·2), W offsets in [0, N·ldw·2).  A conv reads input rows m + a0 + tap·dil: down to a0 rows
 before the activation and (taps − 1)·dil + a0 rows past it, the zero halo rows the caller provides
 (conv.hip: 3·dil rows each side for k = 7, one row each side for a ConvTranspose).  The conv
-epilogue currently launches the pointer form only (gemm.hip pp_use_saddr); its shapes are checked
+epilogue currently launches the pointer form only (gemm_plan.h pp_tile_saddr); its shapes are checked
 all the same, so the scalar form is known to be address-equal for them before anyone switches it on.
 """
 import ctypes

@@ -14,7 +14,8 @@ are the same through HBM or LDS, so the assertion is torch.equal on the bits of 
 
 Forward level: the tiny DiT, S = 192 with both CFG rows conditional (two batch-aligned row tiles),
 planned on 4 CUs so that the projection takes the four-wave tile and the attention whole units;
-ACEHIP_CROSS_FUSE = 0 and 1 run in fresh child processes, the outputs must be byte-equal.
+ACEHIP_CROSS_FUSE = 0 and 1 run in fresh child processes, the outputs must be byte-equal, and each
+child reports the path the forward's rule took and the route gemm() itself plans for that shape.
 """
 import math
 import os
@@ -177,7 +178,9 @@ ff.check(ff.lib().acehip_cross_attn_bf16(ff.ptr(z(2 * S, Dm)), ff.ptr(z(Hh * 128
                                          ff.ptr(z(2 * S, Hh * 128)), 2, S, Hh, KVh, Lenc, Dm, 1e-6, 0.088, -1,
                                          ctypes.byref(path), ff.stream_ptr()))
 torch.cuda.synchronize()
-torch.save({"out": out.cpu(), "path": path.value}, sys.argv[3])
+# gemm()'s own route for the projection under the same environment (acehip_diag_gemm_plan)
+plan = ff.gemm_plan(2 * S, Hh * 128, Dm, 4)
+torch.save({"out": out.cpu(), "path": path.value, "plan": plan}, sys.argv[3])
 """
 
 
@@ -185,7 +188,9 @@ def test_forward_knob_bit_equal(gpu_device, tmp_path):
     """The tiny DiT's forward under ACEHIP_CROSS_FUSE = 0 and 1, each in a fresh process.  M = 2 · 192
     rows × N = 256: 2 × 2 four-wave tiles fill the 4 planned CUs (ACEHIP_GEMM_CUS), and the
     attention's 4 GQA-pair units run whole on attn_fwd_kernel<2> (ACEHIP_ATTN_CUS = 4: 24 one-head
-    units > 1.5 · 4, so not attn_small_kernel)."""
+    units > 1.5 · 4, so not attn_small_kernel).  The four-wave tile is cross_fuse_planned's choice
+    (planned CUs throughout), which the forward follows in both arms; gemm() itself judges a
+    half-chip grid by the device's CUs and plans this small grid as 128² tiles + head_post."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pkg = os.path.join(repo, "ace-step-1.5_amd")
     res = []
@@ -197,5 +202,7 @@ def test_forward_knob_bit_equal(gpu_device, tmp_path):
         assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-2000:])
         res.append(torch.load(dst))
     assert res[0]["path"] == 0 and res[1]["path"] == 1, "the knob must switch the forward's cross path"
+    for r in res:
+        assert (r["plan"]["route"], r["plan"]["v_head"]) == (_ff().ROUTE_STAGED, 0), r["plan"]
     assert torch.isfinite(res[0]["out"].float()).all()
     assert torch.equal(_bits(res[0]["out"]), _bits(res[1]["out"]))

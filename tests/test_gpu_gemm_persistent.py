@@ -2,25 +2,21 @@
 one-tile-per-workgroup launch it replaces: the same bits, because no element's K order changes.
 
 ACEHIP_GEMM_CUS caps the CU count the tile planner fills, so small shapes plan multi-round grids.
-The planner's arithmetic decides which launch a (shape, cap) pair gets (gemm_pick_variant: the
-256-row tile only where ⌈t256 / cus⌉ · 1.093 < ⌈t192 / cus⌉; gemm_tail_split: a last round at most
-60 % full).  Of the first five cases below only (768, 512, 128, cap 2) plans a 256-row grid — the
-other four plan 192-row or 128×128 tiles under either knob value and compare equal without
-reaching the walk — so the cases after them are shapes whose plan does reach each property:
+Every launch first asserts its route (acehip_diag_gemm_plan; tests/test_gemm_plan_host.py holds the
+same rows on the CPU): with the knob on, the walk the case is there for — or, for the four cases
+that plan 192-row or 128×128 tiles, the one grid they take under either knob value; with the knob
+off, anything but the walk.
 
   (768, 512, 128, 2)    6 main tiles, 3 per workgroup, no tail
   (768, 512, 64, 2)     the same walk with a single K-tile: the prologue holds no B(1), so every
                         boundary takes the wait that leaves only the epilogue's stores in flight
-  (1990, 512, 192, 7)   tail split: M1 = 1792 (14 main tiles), 198 tail rows as 4 tiles of 128×256,
-                        the last ones ragged; 18 tiles on 7 workgroups: main, main, tail for
-                        workgroups 0–3; 3 K-tiles (odd)
+  (1990, 512, 192, 7)   tail split: 14 main tiles + 198 tail rows as 4 tiles of 128×256, the last
+                        ones ragged; 18 tiles on 7 workgroups: main, main, tail for workgroups 0–3;
+                        3 K-tiles (odd)
   (1030, 768, 256, 4)   15 main tiles on 4 workgroups (4, 4, 4, 3), no tail; the last row tile has
                         6 live rows and is followed by another tile in its workgroups' walks
-  (1286, 768, 128, 4)   tail split with M1 = 1280 (15 main tiles) and a 6-row tail (3 tiles of
-                        128×256): 18 tiles on 4 workgroups, three of which end on a tail tile
-No planned grid has fewer tiles than planned CUs (a multi-round grid has more by definition, and
-a tail split's main rounds alone fill all but one row of tiles), so the grid's min(CUs, tiles) is
-a guard the dispatch cannot reach; (300, 512, 128, cap 8) runs as 128×128 tiles.
+  (1286, 768, 128, 4)   tail split with a 6-row tail (3 tiles of 128×256): 18 tiles on 4
+                        workgroups, three of which end on a tail tile
 """
 import pytest
 import torch
@@ -34,8 +30,22 @@ pytestmark = pytest.mark.gpu
 
 EPI_SWIGLU = 3
 
-CASES = [(768, 512, 128, 2), (700, 512, 192, 4), (520, 768, 64, 2), (1030, 512, 256, 3), (300, 512, 128, 8),
-         (768, 512, 64, 2), (1990, 512, 192, 7), (1030, 768, 256, 4), (1286, 768, 128, 4)]
+
+
+def _walk(M1, nmain, ntail, grid):
+    return dict(route=5, M1=M1, nmain=nmain, ntail=ntail, grid=grid)   # ACEHIP_ROUTE_WALK
+
+
+def _tile(v):
+    return dict(route=0, v_head=v)   # ACEHIP_ROUTE_TILE
+
+
+# (M, N, K, ACEHIP_GEMM_CUS) → the plan with the walk on
+WANT = {(768, 512, 128, 2): _walk(768, 6, 0, 2), (700, 512, 192, 4): _tile(8), (520, 768, 64, 2): _tile(8),
+        (1030, 512, 256, 3): _tile(8), (300, 512, 128, 8): _tile(0), (768, 512, 64, 2): _walk(768, 6, 0, 2),
+        (1990, 512, 192, 7): _walk(1792, 14, 4, 7), (1030, 768, 256, 4): _walk(1030, 15, 0, 4),
+        (1286, 768, 128, 4): _walk(1280, 15, 3, 4)}
+CASES = list(WANT)
 
 
 def _lib():
@@ -56,6 +66,11 @@ def _swiglu(ff, gpu_device, monkeypatch, A, W, persist, cus):
     N = W.shape[0]
     set_knob(monkeypatch, "ACEHIP_GEMM_CUS", str(cus))
     set_knob(monkeypatch, "ACEHIP_GEMM_PERSIST", "1" if persist else "0")
+    plan, want = ff.gemm_plan(M, N, K, EPI_SWIGLU), WANT[M, N, K, cus]
+    if persist:
+        assert {k: plan[k] for k in want} == want, plan
+    else:
+        assert plan["route"] != ff.ROUTE_WALK, plan
     C = torch.full((M, N // 2), float("nan"), device=gpu_device, dtype=torch.bfloat16)
     ff.check(ff.lib().acehip_gemm_bf16_ex(ff.ptr(A), K, ff.ptr(W), K, ff.ptr(C), N // 2, M, N, K, None,
                                           EPI_SWIGLU, -1, ff.stream_ptr()))

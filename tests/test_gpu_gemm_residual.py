@@ -269,23 +269,21 @@ def test_four_wave_tile_without_helpers_residual_epilogues(gpu_device, monkeypat
 @pytest.mark.parametrize("M,N,rpb,cus,want", [(300, 512, 77, None, 0), (300, 512, 77, 6, 9),
                                               (1100, 512, 333, 8, 8), (2400, 256, 700, 4, 7)])
 def test_production_dispatch_without_splitk(gpu_device, monkeypatch, M, N, rpb, cus, want):
-    """Family 2: variant −1 at K = 128 (2 K-tiles < 8, so gemm() takes no split-K) must run the
-    tile gemm_pick_variant names, whole: bit-identical to that explicit variant, and right
-    against the reference.  The planner, with cus = ACEHIP_GEMM_CUS, nN = N / 256, t7 / t8 / t9 =
-    ceil(M / 256 | 192 | 128)·nN, and use_w4s false throughout (ceil(M / 192)·N / 128 ≤ 50 is far
-    below three quarters of the device's CUs):
-      (300, 512), device CUs:  t8 = 4 ≤ cus / 2 on any device of ≥ 8 CUs            → 0
-      (300, 512), cus 6:       t8 = 4 > 3; t8 = 4 ≤ 6 and t9 = 6 ≤ 6                 → 9
-      (1100, 512), cus 8:      t8 = 12 > 8; c7 = ceil(10 / 8)·1.093 = 2.19 ≥ c8 = 2   → 8
-      (2400, 256), cus 4:      t8 = 13 > 4; c7 = ceil(10 / 4)·1.093 = 3.28 < c8 = 4   → 7
-    The last two are grids gemm_tail_split would split if the epilogue were a store (v 8: 12
-    tiles = 1 round of 8 + 4 ≤ 0.6·8, M1 = 768; v 7: 10 tiles = 2 rounds of 4 + 2 ≤ 0.6·4,
-    M1 = 2048), with a batch boundary on either side of M1: a tail launched for a residual
-    epilogue would read the wrong gate batch and residual rows.
+    """Family 2: variant −1 at K = 128 (2 K-tiles < 8, so gemm() takes no split-K) must run one
+    whole grid of the tile its plan names (asserted through acehip_diag_gemm_plan; the rows stand in
+    tests/test_gemm_plan_host.py): right against the reference, and bit-identical to that explicit
+    variant.  The last two shapes are grids the planner splits for a store epilogue (asserted too),
+    with a batch boundary on either side of M1: a tail launched for a residual epilogue would read
+    the wrong gate batch and residual rows.
     MI355X: overall ≤ 6.5e-6, worst row ≤ 3.9e-3 (one element of a 256-column row at (2400, 256))."""
     K = 128
+    ff = _ff()
     for gated in (False, True):
         with knobs(monkeypatch, ACEHIP_GEMM_CUS=cus):
+            plan = ff.gemm_plan(M, N, K, 1 if gated else 2)
+            assert (plan["route"], plan["v_head"]) == (ff.ROUTE_TILE, want), plan
+            if want in (7, 8):
+                assert ff.gemm_plan(M, N, K, 0)["route"] in (ff.ROUTE_TAIL1, ff.ROUTE_TAIL2)
             prod = check_layouts(gpu_device, M, N, K, rpb, gated, -1, (M, N, cus, gated))
             explicit = run_gemm_res(gpu_device, M, N, K, rpb, gated, want, IN_PLACE)
         assert torch.equal(_bits(prod), _bits(explicit)), f"production dispatch is not variant {want}"
@@ -302,14 +300,16 @@ def test_splitk_epilogue_kernel(gpu_device, monkeypatch, M, N, K):
     partials by gemm_kernel<EPI_PARTIAL> (128×64 tiles by default and with ACEHIP_SPLITK_BN=64,
     128×128 with =128), then splitk_epilogue_kernel's plain and gated branches, in place and out
     of place with ldr = ldc = N + 64 and with ldr = N + 128 != ldc = N + 64.  That the shape really
-    splits on this device (it needs 2·tiles ≤ CUs and the workspace) is asserted first, through
-    the one entry point that reports it: the same GEMM with defer gives deferred == 1.  On 256 CUs:
-    at most 2·16 tiles of 128²; min(16, nk / 4) = 2 or 4 splits, never more than
-    ceil(CUs / grid tiles) ≥ 4 at either width.  K = 1088 is 17 K-tiles: 4 splits of 5, 5, 5 and 2.
+    splits on this device is asserted first, on the plan (2 splits of 4 K-tiles at K = 512; 4 splits
+    of 5, 5, 5 and 2 at K = 1088, 17 K-tiles; the tile width the knob asks for) and through the
+    entry point that reports it: the same GEMM with defer gives deferred == 1.
     Both tile widths sum the same splits in order, so the three settings are bit-identical.
     MI355X: overall ≤ 2.7e-5; worst row ≤ 3.9e-3 at N = 256 (one element), ≤ 9.8e-4 at N = 2048."""
     for bn in (None, "64", "128"):
         with knobs(monkeypatch, ACEHIP_SPLITK_BN=bn):
+            plan = _ff().gemm_plan(M, N, K, 2)
+            assert (plan["route"], plan["splits"], plan["kper"], plan["bn"]) == \
+                (_ff().ROUTE_SPLITK, *((2, 4) if K == 512 else (4, 5)), int(bn or 64)), plan
             assert run_gemm_res_norm(gpu_device, M, N, K, False, False, "rows")[2] == 1, ("no split-K here", bn)
     for gated in (False, True):
         outs = []

@@ -11,20 +11,15 @@ Tile cases: M = 1 (every A row clamps to row 0), 200 (one ragged tile, or two 12
 second ragged), 449 (at 192 rows the last tile has 65 live rows: piece 1 partly clamped, piece 2
 wholly); K = 64 (one K-tile: no B(1), the vmcnt(0) entry), 128 (two), 192 (odd count).
 
-Split kernel (gemm_pp_split_kernel), reached through the production dispatch under ACEHIP_GEMM_CUS:
-  store, (1200, 1024, K ≤ 448, cap 8): 80 tiles of 128², 160 ≤ 256 but fewer than 8 K-tiles, so no
-      split-K.  gemm_pick_variant: t7 = 5·4 = 20, t8 = 7·4 = 28 → ⌈20/8⌉·1.093 = 3.28 < ⌈28/8⌉ = 4,
-      variant 7.  gemm_tail_split: full = 2, rem = 4 (4·5 ≤ 8·3), M1 = (2·8/4)·256 = 1024, the
-      176-row tail as 2·4 = 8 tiles of 128 × 256 (≤ 8 CUs), nmain = 16, a multiple of 8: one launch
-      of 16 + 8 blocks.
-  head-post, B = 2, S = 600 (M = 1200, N = 1024): its 192-row grid is 28 tiles, at most half of
-      the DEVICE's CUs (that test does not use the cap), so it runs as 128² tiles + the standalone
-      head_post kernel under either knob — compared, but it does not reach the split kernel.
-  head-post, B = 2, S = 4200 (M = 8400, N = 2048, K = 128, cap 64): t192 = 44·8 = 352 > 128, so
-      not small; t7 = 33·8 = 264 ≥ 256 and 1·1.093 + 0.6 < ⌈352/256⌉ = 2 → gemm_tail_split(7):
-      264 tiles on 64 CUs, full = 4, rem = 8, M1 = (4·64/8)·256 = 8192, the 208-row tail as
-      2·8 = 16 tiles (≤ 64, the second row of them ragged), nmain = 256: the split kernel, with the
-      batch boundary (row 4200) inside a main tile.
+Split kernel (gemm_pp_split_kernel), reached through the production dispatch under ACEHIP_GEMM_CUS;
+each case asserts its route before it launches (acehip_diag_gemm_plan; the same rows stand in
+tests/test_gemm_plan_host.py):
+  store, (1200, 1024, K ≤ 448, cap 8): one launch of 16 main + 8 tail blocks, M1 = 1024.
+  head-post, B = 2, S = 600 (M = 1200, N = 1024): a small grid by the DEVICE's CU count, so 128²
+      tiles + the standalone head_post kernel under either knob — compared, but it does not reach
+      the split kernel.
+  head-post, B = 2, S = 4200 (M = 8400, N = 2048, K = 128, cap 64): 256 main + 16 tail blocks
+      (the second row of them ragged), M1 = 8192, the batch boundary (row 4200) inside a main tile.
 
 Convs (EPI_CONV through acehip_vae_conv): M = L ≤ a few hundred runs on 64-row tiles
 (gemm_conv: t256 · 4 ≤ CUs); k = 7 at C = 1024 with L = 4200 (68 tiles of 256 rows → 128-row
@@ -32,7 +27,7 @@ tiles) and L = 8300 (132 → 256-row tiles) reaches the other two heights, each 
 tile.
 
 The conv epilogue and the one-launch head-post grid did not pass the round-8 timing rule and stay
-on the pointer form under either knob value (gemm.hip pp_use_saddr), so their cases here (and the
+on the pointer form under either knob value (gemm_plan.h pp_tile_saddr), so their cases here (and the
 S = 600 head-post case, which runs 128² tiles) compare one kernel with itself; they are kept so
 that a later switch of those families is checked the day it is made.
 """
@@ -48,7 +43,7 @@ from acehip.weights import synth_dit_weights
 
 pytestmark = pytest.mark.gpu
 
-EPI_STORE, EPI_RES, EPI_SWIGLU = 0, 2, 3
+EPI_STORE, EPI_RES, EPI_SWIGLU, EPI_HEADPOST = 0, 2, 3, 4
 GUARD = 3      # rows after row M that no launch may touch
 OFF = 24       # elements: operands start 48 bytes into their allocations
 
@@ -137,6 +132,8 @@ def test_split_kernel_store_bit_identical(gpu_device, monkeypatch, K):
     out = {}
     for knob in (0, 1):
         set_knob(monkeypatch, "ACEHIP_GEMM_SADDR", str(knob))
+        plan = ff.gemm_plan(M, N, K, EPI_STORE, lda=K + 64, ldw=K + 64)
+        assert (plan["route"], plan["M1"], plan["nmain"], plan["ntail"], plan["saddr"]) == (ff.ROUTE_TAIL1, 1024, 16, 8, knob), plan
         out[knob] = _run_ex(ff, gpu_device, A, W, R, M, N, K, EPI_STORE, -1)
     torch.cuda.synchronize()
     _assert_same("split store", out[0], out[1])
@@ -163,6 +160,11 @@ def test_headpost_bit_identical(gpu_device, monkeypatch, B, S, nq, nk, nv, K, cu
     out = {}
     for knob in (0, 1):
         set_knob(monkeypatch, "ACEHIP_GEMM_SADDR", str(knob))
+        plan = ff.gemm_plan(M, N, K, EPI_HEADPOST, lda=K + 64, ldw=K)
+        if S == 600:
+            assert (plan["route"], plan["v_head"]) == (ff.ROUTE_STAGED, 0), plan
+        else:
+            assert (plan["route"], plan["M1"], plan["nmain"], plan["ntail"], plan["saddr"]) == (ff.ROUTE_TAIL1, 8192, 256, 16, knob), plan
         qkv = [torch.full((B * n * S + GUARD, 128), float("nan"), device=gpu_device, dtype=torch.bfloat16)
                for n in (nq, nk, nv)]
         ff.check(ff.lib().acehip_gemm_headpost_bf16(ff.ptr(A), K + 64, ff.ptr(W), K, B, S, nq, nk, nv, ff.ptr(qw),

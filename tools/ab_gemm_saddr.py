@@ -9,7 +9,7 @@ production dispatch:
   vae       the whole 240 s decode (T = 6000): its k = 7, k = 1 and ConvTranspose GEMM convs
 (qkv0 and vae missed the rule below in round 8, `profiles/r08a_ab_gemm_saddr.log`, and now launch the
 pointer form under either value: both arms of those two time one kernel until gemm.hip's
-pp_use_saddr routes them again.)
+gemm_plan.h pp_tile_saddr routes them again.)
 Arms alternate inside every round; the default arms 0,1,0 time the pointer form twice per round, so
 each round also gives a same-vs-same spread.  Per round and family the tool prints every arm, and at
 the end whether knob 1 beat the NEARER knob-0 arm in every round by more than twice that round's

@@ -16,7 +16,7 @@ SEPARATE rocprofv3 --pmc passes over the same driver (tools/prof_dit.py), each w
             kept as clock_quotient_GHz.
 
 A SwiGLU call = every EPI_SWIGLU (template epilogue 3) dispatch of one DiT layer: the
-main-grid kernel plus, for a tail-split call, the tail grid (gemm.hip gemm_tail_split).
+main-grid kernel plus, for a tail-split call, the tail grid (gemm_plan.h plan_tail_split).
 Per-call figures sum those dispatch kinds; only kinds launched once per layer of every
 forward (the DiT's 24 × forwards) are counted, so an encoder SwiGLU of another M is not.
 

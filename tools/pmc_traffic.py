@@ -55,7 +55,7 @@ if __name__ == "__main__":
                "kernels": t}
         M = int(sys.argv[4]) if len(sys.argv) > 4 else 6000   # Bc·S of the profiled run
         # one SwiGLU GEMM call = the 256² ping-pong grid over rows [0, M1) + the tail rows as
-        # 128×128 tiles (gemm_tail_split, gemm.hip; 256 CUs, N = 12288 → 48 column tiles)
+        # 128×128 tiles (gemm_plan.h plan_tail_split; 256 CUs, N = 12288 → 48 column tiles)
         M1 = (((M + 255) // 256 * 48) // 256 * 256 // 48) * 256
         keys = [f"gemm_pp_kernel<256, 3> grid={(M1 // 256) * 48 * 512}"]
         if M1 < M:
