@@ -39,7 +39,7 @@ EXPORTS = [
     "acehip_enc_kv_create", "acehip_enc_prefill", "acehip_enc_decode",
     "acehip_attention_decode_ws_bytes", "acehip_attention_decode_bf16", "acehip_lm_head_bf16",
     "acehip_lm_filter_ws_bytes", "acehip_lm_filter",
-    "acehip_diag_pp_src_check", "acehip_diag_gemm_plan",
+    "acehip_diag_pp_src_check", "acehip_diag_gemm_plan", "acehip_diag_attn_plan",
 ]
 
 
@@ -79,6 +79,16 @@ class GemmPlan(ctypes.Structure):
     """acehip_gemm_plan (include/acehip.h)."""
     _fields_ = [(n, c_int) for n in ("route", "v_head", "v_tail", "M1", "nmain", "ntail", "grid", "splits", "kper",
                                      "bn", "stages", "deferred", "saddr", "helpers")]
+
+
+# acehip_attn_plan.kernel (include/acehip.h ACEHIP_ATTN_*)
+ATTN_SMALL, ATTN_PW, ATTN_FWD = 1, 2, 3
+
+
+class AttnPlan(ctypes.Structure):
+    """acehip_attn_plan (include/acehip.h)."""
+    _fields_ = [(n, c_int) for n in ("kernel", "nrep", "window", "units", "unit_tiles", "full", "nsplit", "parts",
+                                     "grid", "block", "persist", "streamk", "sk_nt", "sk_total", "causal", "uses_ws")]
 
 
 _LIB = None
@@ -132,6 +142,8 @@ def _declare(lib):
                                                POINTER(c_int64)]),
         "acehip_diag_gemm_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int, ctypes.c_size_t, c_int, c_int,
                                           POINTER(GemmPlan)]),
+        "acehip_diag_attn_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          POINTER(AttnPlan)]),
         "acehip_gemm_res_norm_bf16": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int64, c_int, c_int,
                                               P, P, P, c_int64, P, c_int, c_float, P, c_int, POINTER(c_int), P]),
         "acehip_attention_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
@@ -249,6 +261,16 @@ def gemm_plan(M, N, K, epi, lda=None, ldw=None, ws_bytes=48 << 20, defer_ok=Fals
     check(lib().acehip_diag_gemm_plan(M, N, K, K if lda is None else lda, K if ldw is None else ldw, epi, ws_bytes,
                                       int(defer_ok), device_cus, ctypes.byref(out)), "diag_gemm_plan")
     return {n: getattr(out, n) for n, _ in GemmPlan._fields_}
+
+
+def attn_plan(B, H, KV, Sq, Sk, window=-1, masked=False, have_ws=True, device_cus=0) -> dict:
+    """The launch the attention dispatch gives a shape under the current ACEHIP_ATTN_* switches
+    (acehip_diag_attn_plan; host only), as a dict of acehip_attn_plan's fields.  device_cus 0: the
+    current device's; have_ws: the split workspace, which the standalone entries and the runtimes pass."""
+    out = AttnPlan()
+    check(lib().acehip_diag_attn_plan(B, H, KV, Sq, Sk, window, int(masked), int(have_ws), device_cus,
+                                      ctypes.byref(out)), "diag_attn_plan")
+    return {n: getattr(out, n) for n, _ in AttnPlan._fields_}
 
 
 def reload_knobs():

@@ -58,7 +58,7 @@ namespace {
 //     with tools/bench_attn.py to size that part of the tile, removed.
 // (ATT_TAU, KT, the mask sentinels NEG / PAST, the asm LDS reads and the tile swizzle kvoff live in
 // attn_tile.h with the per-wave tile body, shared with the fused cross-attention kernel of gemm.hip)
-constexpr int QB = 128;    // queries per workgroup
+constexpr int QB = ATTN_QB;   // queries per workgroup
 
 // tail balancing: units [0, full) run whole; each later unit runs as nsplit
 // KV-range parts whose partial (O, m, l) meet in ws, merged by the last part
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256 * NREP, 3 - NREP) void attn_fwd_kernel(const bf
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
     // work unit u = (b, kvh, q-block), q-block fastest; blocks past sp.full are the
-    // KV-range parts of the tail units (tail balancing, see attention())
+    // KV-range parts of the tail units (tail balancing, attn_plan.h)
     // XCD-aware: the blocks one XCD receives (bid ≡ x mod 8) take a contiguous unit range,
     // so the q-blocks of one (b, kv head) share that XCD's L2 copy of its K/V tiles
     // (whole units only: the tail-split parts must stay the grid's last blocks)
@@ -1368,45 +1368,34 @@ __global__ __launch_bounds__(256, 1) void attn_small_kernel(const bf16_t *__rest
     }
 }
 
+// the split workspace (attention_ws_bytes()) as the kernels take it: tickets, then slabs
+struct AttnWs {
+    int *cnt = nullptr;
+    float *slabs = nullptr;
+};
+AttnWs attn_ws_view(void *ws, int cus) {
+    return {(int *)ws, (float *)((char *)ws + (size_t)attn_ws_slots(cus) * sizeof(int))};
+}
+
 }  // namespace
 
-static int num_cus_attn() {
-    // ACEHIP_ATTN_CUS overrides the CU count the tail split plans for (tests use it
-    // to exercise 3- and 4-way splits on small shapes)
-    return knobs().attn_cus > 0 ? knobs().attn_cus : device_cus();
+// what attn_plan reads besides the shape (attn_plan.h AttnEnv): the CU count the rules plan for
+// — ACEHIP_ATTN_CUS replaces the device's — and the attention switches
+AttnEnv attn_env(int dev_cus) {
+    const Knobs &k = knobs();
+    return {k.attn_cus > 0 ? k.attn_cus : dev_cus > 0 ? dev_cus : device_cus(), k.attn_pw, k.attn_persist, k.attn_small,
+            k.attn_small_mask, k.attn_small_causal, k.attn_streamk};
 }
-
-// short-sequence KV split (a grid of a few units, e.g. the 10 s song's cross-attention: 8
-// units): KV tiles per part.  Turbo 10 s cross
-// (11 tiles, 8 units; tools/gpu_r03z.sh, one process): 1 tile per part 28.5 µs, 2: 22.7, 3: 20.3
-// (DiT song 27.7 / 27.1 / 26.8 ms) — fewer, longer parts pay fewer hand-offs; 4 and 6 tiles
-// (after the slab hand-off, tools/gpu_r03m2.sh): 19.6 / 21.9 vs 19.7 µs, song 25.7 / 26.1 vs 25.6
-// ms; 3 kept
-constexpr int SHORT_TPP = 3;
-// shortest KV loop (tiles) whose tail units are split on attn_pw_kernel: 24 keeps the 240 s band
-// layers (7 tiles) on the persistent walk (tried 7, the tail split: band 48.8 → 57.0 µs, DiT song
-// 490.9 → 493.8 ms, profiles/r06za_band_tailsplit_ab.log)
-constexpr int PW_SPLIT_MIN = 24;
 
 size_t attention_ws_bytes() {
-    const size_t cus = std::max<size_t>(1024, (size_t)num_cus_attn());
-    // [tickets: cus ints][slabs: cus · 8 waves · 66·64 floats]; stream-K uses 2 slabs per workgroup
-    return cus * 8 * 66 * 64 * sizeof(float) + cus * sizeof(int);   // ≤ cus split parts in flight
+    const size_t slots = (size_t)attn_ws_slots(attn_env().cus);
+    return slots * 8 * 66 * 64 * sizeof(float) + slots * sizeof(int);
 }
 
-// mirrors attention()'s choices below for window < 0 and no mask
 bool attention_whole_units(int B, int H, int KV, int Sq, int Sk, bool have_ws) {
     if (B <= 0 || Sq <= 0 || Sk <= 0 || KV <= 0 || H != 2 * KV) return false;
-    const Knobs &kn = knobs();
-    const int cus = num_cus_attn(), nq = (Sq + QB - 1) / QB, unit_tiles = (Sk + KT - 1) / KT;
-    if (kn.attn_small && (int64_t)((Sq + 31) / 32) * H * B <= cus + cus / 2) return false;   // attn_small_kernel
-    if (kn.attn_pw & (Sk == Sq ? 1 : 4)) return false;                                       // attn_pw_kernel
-    const bool short_split = nq * KV * B * 2 <= cus && unit_tiles >= 4;
-    if (short_split) return !have_ws;                       // every unit split over KV ranges
-    if (unit_tiles < 24 && nq * KV * B > cus) return true;  // one head per workgroup, whole units
-    const int units = nq * KV * B, tail = units % cus;
-    if (have_ws && unit_tiles >= 24 && units > cus && tail > 0) return false;   // tail split / stream-K
-    return true;
+    const AttnPlan p = attn_plan(AttnPlanIn{B, H, KV, Sq, Sk, -1, false, have_ws}, attn_env());
+    return p.kernel == ACEHIP_ATTN_FWD && p.nsplit == 1 && !p.streamk;
 }
 
 int attention_fwd_units(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int Sq,
@@ -1421,138 +1410,51 @@ int attention_fwd_units(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_
     return 0;
 }
 
+// The one launch of a plan (attn_plan.h); w: the workspace view where the plan uses it
+static int attn_launch(const AttnPlan &p, const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int H, int KV,
+                       int Sq, int Sk, float sl2, int64_t o_ld, AttnWs w, hipStream_t s, const uint8_t *kmask) {
+    if (p.kernel == ACEHIP_ATTN_SMALL) {
+        attn_small_kernel<<<(unsigned)p.grid, p.block, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, sl2, o_ld, p.parts, w.slabs,
+                                                                w.cnt, kmask, p.causal);
+    } else {
+        SplitArgs sp{(Sq + QB - 1) / QB, p.full, p.nsplit, w.slabs, w.cnt};
+        sp.units = p.persist ? p.units : 0;
+        sp.sk_total = p.sk_total;
+        sp.sk_nt = p.sk_nt;
+        if (p.kernel == ACEHIP_ATTN_PW)
+            attn_pw_kernel<<<p.grid, p.block, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, p.window, sl2, o_ld, sp);
+        else if (p.nrep == 2)
+            attn_fwd_kernel<2><<<p.grid, p.block, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, p.window, sl2, o_ld, sp, kmask);
+        else
+            attn_fwd_kernel<1><<<p.grid, p.block, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, p.window, sl2, o_ld, sp, kmask);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV,
               int Sq, int Sk, int window, float scale, int64_t o_ld, void *ws, hipStream_t s,
               const uint8_t *kmask) {
     if (B <= 0 || Sq <= 0) return 0;
     if (Sk <= 0 || KV <= 0 || H % KV) return fail(-1, "attention: bad heads/lengths");
     if (o_ld % 8) return fail(-1, "attention: o_ld must be a multiple of 8");
-    // a band wider than the sequence (|i − j| ≤ max(Sq, Sk) − 1 ≤ window: every pair admitted)
-    // is full attention — the 10 s songs' sliding layers (S = 125, window 128) then run the full
-    // kernel without per-tile band classification and masks
-    if (window >= 0 && !kmask && std::max(Sq, Sk) - 1 <= window) window = -1;
-    const int grp = H / KV;
-    const float sl2 = scale * 1.4426950408889634f;
-    const int nq = (Sq + QB - 1) / QB;
-    const int cus = num_cus_attn();
-    const int unit_tiles = (window >= 0 && !kmask) ? (QB + 2 * window) / KT + 1 : (Sk + KT - 1) / KT;
-    // heads per workgroup: the GQA pair shares one 8-wave workgroup (K/V staged once per
-    // tile for both heads), or each head gets its own 4-wave workgroup, two per CU, whose
-    // SIMD partners run out of phase. Measured (r02, one box): band −3 %, cross −9 %,
-    // full (47 tiles: the doubled K/V staging dominates) +7 %, cross with fewer pair units
-    // than CUs (B = 1) +11 %, short split-KV cross slower.
-    // 64-row-per-wave kernel for the DiT's unmasked GQA-pair layers: ACEHIP_ATTN_PW = bit mask of
-    // the layer kinds that use it (1 full, 2 band, 4 cross = window < 0 with Sk != Sq).  r02 A/B
-    // (tools/bench_attn.py, one process, three boxes): band 46.4-48.4 vs 47.6-48.8 µs (kept),
-    // full 166-189 vs 161-179 and B = 1 cross 30.5-31.8 vs 29.6-30.6 (stay on attn_fwd_kernel)
-    const Knobs &kn = knobs();
-    const int pw_mask = kn.attn_pw;
-    const int kind_bit = window >= 0 ? 2 : (Sk == Sq ? 1 : 4);
-    // attn_small_kernel where its grid is at most 1.5 rounds of one-head × 32-row units (measured,
-    // tools/bench_attn.py, one process, profiles/r05an_attn_small_vs_fwd.log: B = 2 full / cross at
-    // S = 125 8.6 / 13.5 vs 15.6 / 26.7 µs, S = 375 (384 units) 21.6 / 29.1 vs 24.6 / 30.6; at
-    // S = 750 (768 units) 45.1 / 43.0 vs 34.8 / 34.0 — attn_fwd_kernel's 128-row GQA-pair units
-    // read K / V once per pair and tile, and win once the grid fills the chip)
-    const int64_t small_units = (int64_t)((Sq + 31) / 32) * H * B;
-    const bool small_causal = window == ATTN_CAUSAL && !kmask && kn.attn_small_causal;
-    if (kn.attn_small && window < 0 && (window != ATTN_CAUSAL || small_causal) && small_units <= cus + cus / 2 &&
-        (!kmask || kn.attn_small_mask)) {
-        const int64_t units = small_units;
-        // KV parts per unit: about one tile per wave while the grid stays within one round
-        // (ACEHIP_ATTN_SMALL=2: no parts)
-        int parts = 1;
-        const int ntall = (Sk + KT - 1) / KT;
-        if (ws && kn.attn_small == 1 && units <= std::max(1024, cus))
-            parts = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(ntall + 3) / 4, cus / units, 16}));
-        attn_small_kernel<<<(unsigned)(units * parts), 256, 0, s>>>(
-            q, k, v, o, H, KV, Sq, Sk, sl2, o_ld, parts,
-            parts > 1 ? (float *)((char *)ws + (size_t)std::max(1024, cus) * sizeof(int)) : nullptr,
-            parts > 1 ? (int *)ws : nullptr, kmask, small_causal ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (grp == 2 && !kmask && window != ATTN_CAUSAL && (pw_mask & kind_bit)) {
-        const int units = nq * KV * B;
-        SplitArgs sp{nq, units, 1, nullptr, nullptr};
-        const int tail = units % cus;
-        if (ws && unit_tiles >= PW_SPLIT_MIN && units > cus && tail > 0 && tail <= cus / 2) {
-            sp.full = units - tail;
-            sp.nsplit = min(4, cus / tail);
-        } else if (ws && window < 0 && units * 2 <= cus && unit_tiles >= 4) {
-            sp.full = 0;
-            sp.nsplit = min(min(cus / units, (unit_tiles + SHORT_TPP - 1) / SHORT_TPP), 16);
-        }
-        if (sp.nsplit > 1) {
-            sp.cnt = (int *)ws;
-            sp.ws = (float *)((char *)ws + (size_t)std::max(1024, cus) * sizeof(int));
-        }
-        int grid = sp.full + (units - sp.full) * sp.nsplit;
-        // band layers with more units than CUs: one persistent workgroup per CU walking units
-        // blockIdx.x + k·grid as one KV-tile stream (every unit then has ≥ 2 tiles: window ≥ KT,
-        // Sq = Sk > 2·KT).  ACEHIP_ATTN_PERSIST=0 restores one workgroup per unit (A/B)
-        if (kn.attn_persist && sp.nsplit == 1 && window >= KT && Sq == Sk && Sq > 2 * KT && units > cus) {
-            sp.units = units;
-            grid = cus;
-        }
-        attn_pw_kernel<<<grid, 256, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, window, sl2, o_ld, sp);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const bool short_split = window < 0 && nq * KV * B * 2 <= cus && unit_tiles >= 4;
-    const bool split_heads = grp == 2 && window != ATTN_CAUSAL &&
-                             unit_tiles < 24 && !short_split && nq * KV * B > cus;
-    const int nrep = split_heads ? 1 : grp;
-    const int units = nq * KV * (grp / nrep) * B;
-    SplitArgs sp{nq, units, 1, nullptr, nullptr};
-    // one workgroup per CU: a partial last round of whole units is replaced by
-    // tail units split over ⌊CUs / tail⌋ KV ranges (1.5 rounds instead of 2 at
-    // 384 units on 256 CUs)
-    const int tail = units % cus;
-    // only long KV loops pay for the partial write + merge (measured: full attention
-    // at S = 3000, 47 tiles, −27 %; band (≈7 tiles) and cross (11 tiles) lose)
-    if (window == ATTN_CAUSAL) {
-        // causal (text encoder): whole units only — a KV-range part past the diagonal
-        // would hold no valid key
-    } else if (ws && nrep == 2 && unit_tiles >= 24 && units > cus && tail > 0 && tail <= cus / 2) {
-        sp.full = units - tail;
-        sp.nsplit = min(4, cus / tail);
-        sp.cnt = (int *)ws;
-        sp.ws = (float *)((char *)ws + (size_t)std::max(1024, cus) * sizeof(int));
-    } else if (ws && nrep == 2 && short_split) {
-        // short sequences (a few query blocks): every unit split over KV ranges so the
-        // grid reaches the CUs (cross-attention of a 10 s song: 8 units → 40 parts)
-        sp.full = 0;
-        sp.nsplit = min(min(cus / units, (unit_tiles + SHORT_TPP - 1) / SHORT_TPP), 16);
-        sp.cnt = (int *)ws;
-        sp.ws = (float *)((char *)ws + (size_t)std::max(1024, cus) * sizeof(int));
-    }
-    int grid = sp.full + (units - sp.full) * sp.nsplit;
-    // stream-K (ACEHIP_ATTN_STREAMK): unmasked full layers whose units do not divide into whole
-    // rounds run as ONE round of `cus` workgroups over the units' concatenated KV tiles, instead
-    // of a whole round + tail-split parts (a second round's fixed cost).  240 s full attention
-    // (384 units × 47 tiles on 256 CUs) 186.1 → 175.8 µs in one process; the one-round cross grid
-    // (192 units × 11 tiles) loses, 34.8 → 45.8 (its pieces' restart + merge ≥ the 2.75 tiles
-    // saved), so only grids of more units than CUs and long loops take it
-    // (two slab slots per workgroup: 2·cus ≤ the workspace's 1024 slots)
-    if (kn.attn_streamk && ws && nrep == 2 && window < 0 && !kmask && units > cus && units % cus != 0 &&
-        unit_tiles >= 24 && 2 * (size_t)cus <= (size_t)std::max(1024, cus)) {
-        const size_t wcus = (size_t)std::max(1024, cus);
-        sp = SplitArgs{nq, units, 1, nullptr, nullptr};
-        sp.sk_nt = unit_tiles;
-        sp.sk_total = units * unit_tiles;
-        sp.cnt = (int *)ws;
-        sp.ws = (float *)((char *)ws + wcus * sizeof(int));
-        grid = cus;
-    }
-    if (nrep == 2) {
-        attn_fwd_kernel<2><<<grid, 512, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, window, sl2, o_ld, sp, kmask);
-    } else if (nrep == 1) {
-        attn_fwd_kernel<1><<<grid, 256, 0, s>>>(q, k, v, o, H, KV, Sq, Sk, window, sl2, o_ld, sp, kmask);
-    } else {
-        return fail(-1, "attention: heads/kv_heads must be 1 or 2");
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const AttnEnv env = attn_env();
+    const AttnPlan p = attn_plan(AttnPlanIn{B, H, KV, Sq, Sk, window, kmask != nullptr, ws != nullptr}, env);
+    if (!p.kernel) return fail(-1, "attention: heads/kv_heads must be 1 or 2");
+    return attn_launch(p, q, k, v, o, H, KV, Sq, Sk, scale * 1.4426950408889634f, o_ld,
+                       p.uses_ws ? attn_ws_view(ws, env.cus) : AttnWs{}, s, kmask);
 }
 
 }  // namespace acehip
+
+// Host-only window on the dispatch (tests; no kernel launch): the plan attention() would launch from
+extern "C" int acehip_diag_attn_plan(int B, int H, int KV, int Sq, int Sk, int window, int masked, int have_ws,
+                                     int device_cus, acehip_attn_plan *out) {
+    using namespace acehip;
+    if (!out || B <= 0 || Sq <= 0 || Sk <= 0 || KV <= 0 || H <= 0 || H % KV || device_cus < 0)
+        return fail(ACEHIP_E_ARG, "diag_attn_plan: a shape attention() refuses or skips, or a null plan");
+    *out = attn_plan(AttnPlanIn{B, H, KV, Sq, Sk, window, masked != 0, have_ws != 0}, attn_env(device_cus));
+    if (!out->kernel) return fail(ACEHIP_E_ARG, "diag_attn_plan: heads/kv_heads must be 1 or 2");
+    return 0;
+}
+

@@ -38,8 +38,8 @@ namespace {
 
 constexpr float LOG2E_D = 1.4426950408889634f;
 constexpr int PART_STRIDE = 132;     // floats per (head, part): m, l, 2 pad, o[128] (16-B aligned)
-constexpr int KEYS_PER_STEP = 64;    // 4 waves × 16 keys
-constexpr int MAX_PARTS = 64;
+constexpr int KEYS_PER_STEP = DECODE_KEYS_PER_STEP;   // 4 waves × 16 keys (attn_plan.h)
+constexpr int MAX_PARTS = DECODE_MAX_PARTS;
 
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -189,10 +189,6 @@ __global__ __launch_bounds__(128) void attn_decode_fold_kernel(const float *__re
     o[bh * 128 + d] = f2bf(l > 0.f ? acc / l : 0.f);
 }
 
-int decode_cus() {
-    return knobs().attn_cus > 0 ? knobs().attn_cus : device_cus();
-}
-
 // ------------------------------------------------------------------ lm_head ---
 template <int MB, int R>
 __global__ __launch_bounds__(256) void lm_head_kernel(const bf16_t *__restrict__ x, int64_t ldx,
@@ -252,13 +248,8 @@ int attention_decode(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *
     if (G != 1 && G != 2 && G != 4) return fail(-1, "attention_decode: heads/kv_heads must be 1, 2 or 4");
     if (n <= 0 || n > cap) return fail(-1, "attention_decode: need 0 < n <= cap");
     if (kmask && mask_ld < n) return fail(-1, "attention_decode: mask_ld < n");
-    // key ranges of whole 64-key steps, about two workgroups per CU (four per CU measured slower
-    // at 2304 keys, B·KV = 16: 26.1 vs 22.2 µs — more partials to write and fold)
-    const int steps = (n + KEYS_PER_STEP - 1) / KEYS_PER_STEP;
-    int parts = std::min({steps, std::max(1, 2 * decode_cus() / (B * KV)), MAX_PARTS});
-    if (!ws || ws_bytes < attention_decode_ws_bytes(B, H)) parts = 1;
-    const int per = (steps + parts - 1) / parts;
-    parts = (steps + per - 1) / per;
+    const bool have_ws = ws && ws_bytes >= attention_decode_ws_bytes(B, H);
+    const auto [parts, per] = attn_decode_plan(B, KV, n, have_ws, attn_env().cus);   // key ranges (attn_plan.h)
     const dim3 grid((unsigned)parts, (unsigned)KV, (unsigned)B);
     const float sl2 = scale * LOG2E_D;
     const int kper = per * KEYS_PER_STEP;

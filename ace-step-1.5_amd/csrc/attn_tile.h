@@ -14,7 +14,7 @@
 namespace acehip {
 
 constexpr float ATT_TAU = 8.0f;   // lazy-rescale threshold (0: rescale on every new max)
-constexpr int KT = 64;            // keys per tile
+constexpr int KT = ATTN_KT;       // keys per tile
 constexpr int KV_TILE = KT * 256; // one K or V tile image: 64 rows × 256 B
 // Sentinels are powers of two so that NEG·sl2 is exact: the exp2 argument
 // fmaf(NEG, sl2, −m) of a row whose max IS the sentinel is then exactly 0

@@ -1,6 +1,7 @@
 // kernels.h — launchers for every device kernel of libacehip (internal C++ API).
 #pragma once
 #include "common.h"
+#include "attn_plan.h"
 #include "gemm_plan.h"
 
 namespace acehip {
@@ -39,7 +40,7 @@ struct Knobs {
 };
 const Knobs &knobs();
 // compute units of the current device (256 if the query fails), read once per process; every
-// planner puts its own policy on top (gemm.hip plan_env, num_cus_attn, decode_cus)
+// planner puts its own policy on top (gemm.hip plan_env, attention.hip attn_env)
 int device_cus();
 
 // ------------------------------------------------------------------ GEMM ---
@@ -173,15 +174,18 @@ int head_post(const HeadPostArgs &a, hipStream_t s);
 // ws: attention_ws_bytes() of zero-initialised device memory (tail-split partials
 // + self-resetting counters), or null to disable tail balancing.
 // kmask: optional key-padding mask [B][Sk] (1 = attend), encoder semantics (attention.hip header)
-// window: < 0 full, >= 0 band |i−j| <= window, ATTN_CAUSAL keys j <= i (Qwen3 text encoder)
-constexpr int ATTN_CAUSAL = -2;
+// window: < 0 full, >= 0 band |i−j| <= window, ATTN_CAUSAL keys j <= i (attn_plan.h)
+// attention() checks its arguments, plans (attn_plan.h attn_plan under attn_env()) and launches
+// the plan; attn_env: the planned CU count (ACEHIP_ATTN_CUS, else dev_cus, else the device's) and
+// the attention switches — attention_decode's key-range split plans for the same count
+AttnEnv attn_env(int dev_cus = 0);
 int attention(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV,
               int Sq, int Sk, int window, float scale, int64_t o_ld, void *ws, hipStream_t s,
               const uint8_t *kmask = nullptr);
 size_t attention_ws_bytes();
-// Whether attention() runs this unmasked, unwindowed shape as whole units on attn_fwd_kernel (no
-// attn_small_kernel, attn_pw_kernel, KV split or stream-K): the fused cross kernel's per-wave
-// arithmetic is that path's.  attention_fwd_units launches exactly that, whatever the CU count.
+// Whether attention()'s plan runs this unmasked, unwindowed GQA-pair shape as whole units on
+// attn_fwd_kernel (no attn_small_kernel, attn_pw_kernel, KV split or stream-K): the fused cross
+// kernel's per-wave arithmetic is that path's.  attention_fwd_units launches exactly that, whatever the CU count.
 bool attention_whole_units(int B, int H, int KV, int Sq, int Sk, bool have_ws);
 int attention_fwd_units(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int Sq,
                         int Sk, float scale, int64_t o_ld, hipStream_t s);

@@ -495,6 +495,39 @@ typedef struct acehip_gemm_plan {
 int acehip_diag_gemm_plan(int M, int N, int K, int64_t lda, int64_t ldw, int epi, size_t ws_bytes, int defer_ok,
                           int device_cus, acehip_gemm_plan *out);
 
+/* The launch acehip_attention_bf16 / acehip_attention_masked_bf16 and the runtimes' attention
+ * layers give a shape: the value the library's dispatch plans before it launches
+ * (csrc/attn_plan.h holds the rules).  Fields a route does not use are 0. */
+enum {
+    ACEHIP_ATTN_SMALL = 1,    /* attn_small_kernel: one head x 32 query rows per workgroup, `parts` KV parts per unit */
+    ACEHIP_ATTN_PW = 2,       /* attn_pw_kernel: a GQA pair x 128 query rows, 64 rows per wave */
+    ACEHIP_ATTN_FWD = 3       /* attn_fwd_kernel<nrep>: nrep heads x 128 query rows, 32 rows per wave */
+};
+typedef struct acehip_attn_plan {
+    int kernel;               /* ACEHIP_ATTN_* */
+    int nrep;                 /* query heads per workgroup */
+    int window;               /* as launched: a band at least as wide as the sequence has become -1 (full) */
+    int units, unit_tiles;    /* work units (a workgroup's heads x its query rows) and KV tiles of 64 keys per unit */
+    int full, nsplit;         /* pw / fwd: units [0, full) run whole, each later one as nsplit KV-range parts
+                                 (tail split: 0 < full < units; short split: full 0; whole units: full = units, nsplit 1) */
+    int parts;                /* small: KV parts per unit */
+    int grid, block;          /* workgroups and threads per workgroup of the launch */
+    int persist;              /* pw: `grid` persistent workgroups walk the units */
+    int streamk;              /* fwd: `grid` workgroups share the sk_total = units x sk_nt concatenated KV tiles */
+    int sk_nt, sk_total;
+    int causal;               /* window is -2: keys j <= i */
+    int uses_ws;              /* the launch gets the ticket and slab pointers of the split workspace */
+} acehip_attn_plan;
+
+/* Host-only, for tests (no kernel launch): the plan of q [B,H,Sq,128] x k/v [B,KV,Sk,128] with
+ * `window` (as acehip_attention_bf16), with a key-padding mask if masked and with the split
+ * workspace if have_ws (the standalone entries and the runtimes always pass one) — under the
+ * ACEHIP_ATTN_* switches of the environment (ACEHIP_ATTN_CUS included) on a device of device_cus
+ * compute units (0: the current device's).  Shapes the dispatch refuses (and empty ones, which it
+ * skips) return ACEHIP_E_ARG. */
+int acehip_diag_attn_plan(int B, int H, int KV, int Sq, int Sk, int window, int masked, int have_ws,
+                          int device_cus, acehip_attn_plan *out);
+
 /* A residual GEMM and the norm that consumes it, as the DiT layer issues the pair (tests):
  *   X[0:M] = residual epilogue (as above, in place, N = ldc = D) of A[M,K] · W[D,K]^T
  *   X[from:M_norm] = bf16(X + v[D])                         (v != NULL; M <= from <= M_norm)

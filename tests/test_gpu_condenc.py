@@ -54,9 +54,13 @@ def test_masked_attention_small(gpu_device, monkeypatch, H, KV, S, valid):
     """Key-padding-masked full attention on attn_small_kernel (ACEHIP_ATTN_SMALL_MASK, the
     encoders' short grids; KV parts through the workspace at S = 1000): against SDPA
     with the reference's additive mask — an all-masked row (valid 0) is uniform over its S keys —
-    and against attn_fwd_kernel's masked mode (=0)."""
+    and against attn_fwd_kernel's masked mode (=0), whose route is whole units (S = 77, and one
+    head per workgroup at H = KV) or the short split (S = 300: 2 parts, S = 1000: 6 parts).  Each
+    arm asserts its route (acehip_diag_attn_plan; the rows stand in tests/test_attn_plan_host.py)."""
     from acehip import _ffi as ff
     B = len(valid)
+    parts = {300: 1, 1000: 2, 77: 1, 250: 1}[S]                                   # attn_small_kernel's KV parts
+    fwd = {300: (2, 48, 2), 1000: (2, 16, 6), 77: (2, 4, 1), 250: (1, 64, 1)}[S]   # nrep, units, nsplit
     g = torch.Generator().manual_seed(S * 3 + H)
     q = torch.randn(B, H, S, 128, generator=g).bfloat16()
     k = torch.randn(B, KV, S, 128, generator=g).bfloat16()
@@ -74,6 +78,12 @@ def test_masked_attention_small(gpu_device, monkeypatch, H, KV, S, valid):
     outs = {}
     for mode in ("1", "0"):
         set_knob(monkeypatch, "ACEHIP_ATTN_SMALL_MASK", mode)
+        plan = ff.attn_plan(B, H, KV, S, S, -1, masked=True)
+        if mode == "1":
+            assert (plan["kernel"], plan["units"], plan["parts"]) == (ff.ATTN_SMALL, (S + 31) // 32 * H * B, parts), plan
+        else:
+            assert (plan["kernel"], plan["nrep"], plan["units"], plan["nsplit"], plan["streamk"]) == \
+                (ff.ATTN_FWD,) + fwd + (0,), plan
         o = torch.full((B, S, H * 128), float("nan"), device=gpu_device, dtype=torch.bfloat16)
         ff.check(ff.lib().acehip_attention_masked_bf16(ff.ptr(qd), ff.ptr(kd), ff.ptr(vd), ff.ptr(o), B, H, KV, S,
                                                        S, -1, 128 ** -0.5, ff.ptr(km), ff.stream_ptr()))
@@ -314,7 +324,9 @@ def test_overlapped_text_encoder_feeds_condition_encoder(gpu_device):
 def test_causal_attention_small(gpu_device, monkeypatch, B, H, KV, S):
     """Unmasked causal attention (the Qwen3 text encoder, 28 layers per song) on attn_small_kernel
     (ACEHIP_ATTN_SMALL_CAUSAL): each one-head x 32-row unit walks its keys up to its last row's
-    diagonal.  vs fp32 SDPA with is_causal and vs attn_fwd_kernel's causal mode (knob off)."""
+    diagonal.  vs fp32 SDPA with is_causal and vs attn_fwd_kernel's causal mode (knob off: whole
+    units, the GQA pair — or at H = KV the single head — per workgroup).  Each arm asserts its route
+    (acehip_diag_attn_plan; the rows stand in tests/test_attn_plan_host.py)."""
     import math
     from acehip import _ffi as ff
     from conftest import rel_l2, set_knob
@@ -325,6 +337,12 @@ def test_causal_attention_small(gpu_device, monkeypatch, B, H, KV, S):
 
     def run(on):
         set_knob(monkeypatch, "ACEHIP_ATTN_SMALL_CAUSAL", "1" if on else "0")
+        plan = ff.attn_plan(B, H, KV, S, S, -2)
+        if on:
+            assert (plan["kernel"], plan["units"], plan["causal"]) == (ff.ATTN_SMALL, (S + 31) // 32 * H * B, 1), plan
+        else:
+            assert (plan["kernel"], plan["nrep"], plan["units"], plan["nsplit"], plan["streamk"], plan["causal"]) == \
+                (ff.ATTN_FWD, min(H // KV, 2), (S + 127) // 128 * KV * B, 1, 0, 1), plan
         o = torch.full((B, S, H * 128), float("nan"), device=gpu_device, dtype=torch.bfloat16)
         ff.check(ff.lib().acehip_attention_bf16(ff.ptr(q), ff.ptr(k), ff.ptr(v), ff.ptr(o), B, H, KV, S, S, -2,
                                                 1 / math.sqrt(128), ff.stream_ptr()))

@@ -180,7 +180,9 @@ ff.check(ff.lib().acehip_cross_attn_bf16(ff.ptr(z(2 * S, Dm)), ff.ptr(z(Hh * 128
 torch.cuda.synchronize()
 # gemm()'s own route for the projection under the same environment (acehip_diag_gemm_plan)
 plan = ff.gemm_plan(2 * S, Hh * 128, Dm, 4)
-torch.save({"out": out.cpu(), "path": path.value, "plan": plan}, sys.argv[3])
+# and attention()'s for the cross-attention (acehip_diag_attn_plan)
+attn_plan = ff.attn_plan(2, Hh, KVh, S, Lenc)
+torch.save({"out": out.cpu(), "path": path.value, "plan": plan, "attn_plan": attn_plan}, sys.argv[3])
 """
 
 
@@ -204,5 +206,8 @@ def test_forward_knob_bit_equal(gpu_device, tmp_path):
     assert res[0]["path"] == 0 and res[1]["path"] == 1, "the knob must switch the forward's cross path"
     for r in res:
         assert (r["plan"]["route"], r["plan"]["v_head"]) == (_ff().ROUTE_STAGED, 0), r["plan"]
+        ap = r["attn_plan"]
+        assert (ap["kernel"], ap["nrep"], ap["units"], ap["nsplit"], ap["streamk"], ap["grid"]) == \
+            (_ff().ATTN_FWD, 2, 4, 1, 0, 4), ap
     assert torch.isfinite(res[0]["out"].float()).all()
     assert torch.equal(_bits(res[0]["out"]), _bits(res[1]["out"]))

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from conftest import set_knob, cosine, golden_manifest, load_golden, rel_l2
 
+from acehip._ffi import ATTN_FWD, ATTN_PW, ATTN_SMALL
 from acehip.config import DiTConfig
 from acehip.weights import synth_dit_weights
 from oracle import dit_oracle, sampler_oracle
@@ -85,31 +86,99 @@ def _gemm_variant_check(gpu_device, variant, M, N, K):
     assert rel_l2(Cs.float().cpu(), refs.cpu()) < 1e-2
 
 
+def _assert_attn_route(ff, shape, masked=False, **want):
+    """The launch attention() plans for shape = (B, H, KV, Sq, Sk, window) under the current switches
+    (acehip_diag_attn_plan; the same rows stand in tests/test_attn_plan_host.py), asserted before
+    the launch.  Rows with ACEHIP_ATTN_CUS unset are planned for the MI355X's 256 CUs."""
+    plan = ff.attn_plan(*shape, masked=masked)
+    assert {k: plan[k] for k in want} == want, (shape, plan)
+    return plan
+
+
 @pytest.mark.parametrize("cus,window", [(16, -1), (18, -1), (20, -1)])
 @pytest.mark.parametrize("pw", ["0", "7"])
 def test_attention_tail_split(gpu_device, monkeypatch, cus, window, pw):
-    """Tail balancing with 2-, 3- and 4-way KV splits (24 units; CU count 16/18/20 → tail 8/6/4 →
-    nsplit 2/3/4; overridden so small
-    shapes take the split path): merged partials must match the fp32 reference."""
+    """Tail balancing with 2-, 3- and 4-way KV splits (24 units of 25 KV tiles; CU count 16/18/20 →
+    tail 8/6/4 → nsplit 2/3/4; overridden so small shapes take the split path): merged partials
+    must match the fp32 reference.  pw "7": the split on attn_pw_kernel.  pw "0": under the default
+    ACEHIP_ATTN_STREAMK=1 stream-K takes this shape instead (as test_attention_streamk's first row),
+    so a second arm with ACEHIP_ATTN_STREAMK=0 runs the split on attn_fwd_kernel<2>."""
     set_knob(monkeypatch, "ACEHIP_ATTN_CUS", str(cus))
     set_knob(monkeypatch, "ACEHIP_ATTN_PW", pw)
     ff = _lib()
     B, H, KV, Sq, Sk = 2, 4, 2, 700, 1600       # 6 q-blocks x 2 KV x 2 = 24 units, 25 KV tiles
+    split = dict(units=24, unit_tiles=25, full=cus, nsplit={16: 2, 18: 3, 20: 4}[cus], streamk=0, uses_ws=1)
     g = torch.Generator(device="cpu").manual_seed(cus * 3 + window)
     q = torch.randn(B, H, Sq, 128, generator=g).to(gpu_device, torch.bfloat16)
     k = torch.randn(B, KV, Sk, 128, generator=g).to(gpu_device, torch.bfloat16)
     v = torch.randn(B, KV, Sk, 128, generator=g).to(gpu_device, torch.bfloat16)
+    ref = _attn_ref(q, k, v, window).transpose(1, 2).reshape(B, Sq, H * 128).float().cpu()
+    for streamk in (None, "0") if pw == "0" else (None,):
+        if streamk is not None:
+            set_knob(monkeypatch, "ACEHIP_ATTN_STREAMK", streamk)
+        if pw == "7":
+            _assert_attn_route(ff, (B, H, KV, Sq, Sk, window), kernel=ff.ATTN_PW, **split)
+        elif streamk == "0":
+            _assert_attn_route(ff, (B, H, KV, Sq, Sk, window), kernel=ff.ATTN_FWD, nrep=2, **split)
+        else:
+            _assert_attn_route(ff, (B, H, KV, Sq, Sk, window), kernel=ff.ATTN_FWD, nrep=2, streamk=1, grid=cus)
+        outs = []
+        for _ in range(3):                          # later launches check the counters self-reset
+            o = torch.empty(B, Sq, H * 128, device=gpu_device, dtype=torch.bfloat16)
+            ff.check(ff.lib().acehip_attention_bf16(ff.ptr(q), ff.ptr(k), ff.ptr(v), ff.ptr(o), B, H, KV, Sq, Sk,
+                                                    window, 1 / math.sqrt(128), ff.stream_ptr()))
+            torch.cuda.synchronize()
+            assert rel_l2(o.float().cpu(), ref) < 1e-2
+            outs.append(o)
+        # the parts are merged in part order whichever finishes last: bit-reproducible
+        assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+
+
+@pytest.mark.parametrize("pw,cus", [("0", 0), ("0", 16), ("7", 0), ("7", 16), (None, 0)])
+def test_attention_short_split(gpu_device, monkeypatch, pw, cus):
+    """The short split: a grid of at most half the CUs in units runs every unit as nsplit KV-range
+    parts (full = 0) — the cross-attention of one conditional row at S = 769 … 2048 patches.
+    pw None: that production shape under default switches (S = 1000: 64 units of 11 tiles on
+    attn_fwd_kernel<2>, 4 parts each).  Else the smallest shape, with ACEHIP_ATTN_SMALL=0 (6 units of
+    11 tiles, a last query block of one row and a last key tile of one key) on attn_fwd_kernel<2>
+    ("0") and attn_pw_kernel ("7"): 4 parts where ⌈tiles / 3⌉ limits them, 2 where cus / units does
+    (ACEHIP_ATTN_CUS=16).  Against the fp32 reference, bit-identical over three launches."""
+    ff = _lib()
+    if pw is None:
+        B, H, KV, Sq, Sk = 1, 16, 8, 1000, 641
+        want = dict(kernel=ff.ATTN_FWD, nrep=2, units=64, unit_tiles=11, full=0, nsplit=4, grid=256)
+    else:
+        B, H, KV, Sq, Sk = 1, 4, 2, 257, 641
+        set_knob(monkeypatch, "ACEHIP_ATTN_SMALL", "0")
+        set_knob(monkeypatch, "ACEHIP_ATTN_PW", pw)
+        if cus:
+            set_knob(monkeypatch, "ACEHIP_ATTN_CUS", str(cus))
+        nsplit = 2 if cus else 4
+        want = dict(kernel=ff.ATTN_PW if pw == "7" else ff.ATTN_FWD, nrep=2, units=6, unit_tiles=11, full=0,
+                    nsplit=nsplit, grid=6 * nsplit)
+    _assert_attn_route(ff, (B, H, KV, Sq, Sk, -1), streamk=0, uses_ws=1, **want)
+    g = torch.Generator(device="cpu").manual_seed(Sq * 7 + Sk + cus)
+    q = torch.randn(B, H, Sq, 128, generator=g).to(gpu_device, torch.bfloat16)
+    k = torch.randn(B, KV, Sk, 128, generator=g).to(gpu_device, torch.bfloat16)
+    v = torch.randn(B, KV, Sk, 128, generator=g).to(gpu_device, torch.bfloat16)
+    ref = _attn_ref(q, k, v, -1).transpose(1, 2).reshape(B, Sq, H * 128).float().cpu()
     outs = []
-    for _ in range(3):                          # later launches check the counters self-reset
-        o = torch.empty(B, Sq, H * 128, device=gpu_device, dtype=torch.bfloat16)
-        ff.check(ff.lib().acehip_attention_bf16(ff.ptr(q), ff.ptr(k), ff.ptr(v), ff.ptr(o), B, H, KV, Sq, Sk,
-                                                window, 1 / math.sqrt(128), ff.stream_ptr()))
+    for _ in range(3):
+        o = torch.full((B, Sq, H * 128), float("nan"), device=gpu_device, dtype=torch.bfloat16)
+        ff.check(ff.lib().acehip_attention_bf16(ff.ptr(q), ff.ptr(k), ff.ptr(v), ff.ptr(o), B, H, KV, Sq, Sk, -1,
+                                                1 / math.sqrt(128), ff.stream_ptr()))
         torch.cuda.synchronize()
-        ref = _attn_ref(q, k, v, window).transpose(1, 2).reshape(B, Sq, H * 128)
-        assert rel_l2(o.float().cpu(), ref.float().cpu()) < 1e-2
+        assert rel_l2(o.float().cpu(), ref) < 1e-2
         outs.append(o)
-    # the parts are merged in part order whichever finishes last: bit-reproducible
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+
+
+# KV parts per unit of test_attention_small's rows under ACEHIP_ATTN_SMALL=1:
+# min(⌈tiles / 4⌉, cus / units, 16), at least 1
+_SMALL_PARTS = {(1, 16, 8, 125, 641, 0): 3, (1, 16, 8, 125, 125, 0): 1, (2, 16, 8, 125, 641, 0): 2,
+                (1, 16, 8, 1, 641, 0): 3, (1, 2, 1, 33, 65, 0): 1, (3, 4, 2, 77, 1000, 0): 4,
+                (1, 16, 16, 200, 2000, 0): 2, (1, 16, 8, 125, 641, 100): 1, (1, 4, 2, 31, 3000, 64): 12,
+                (1, 2, 1, 40, 1, 0): 1}
 
 
 @pytest.mark.parametrize("B,H,KV,Sq,Sk,cus", [(1, 16, 8, 125, 641, 0), (1, 16, 8, 125, 125, 0),
@@ -134,6 +203,8 @@ def test_attention_small(gpu_device, monkeypatch, B, H, KV, Sq, Sk, cus):
     outs = {}
     for mode in ("1", "2"):
         set_knob(monkeypatch, "ACEHIP_ATTN_SMALL", mode)
+        _assert_attn_route(ff, (B, H, KV, Sq, Sk, -1), kernel=ff.ATTN_SMALL, units=(Sq + 31) // 32 * H * B,
+                           parts=_SMALL_PARTS[B, H, KV, Sq, Sk, cus] if mode == "1" else 1)
         runs = []
         for _ in range(3):
             o = torch.full((B, Sq, H * 128), float("nan"), device=gpu_device, dtype=torch.bfloat16)
@@ -154,9 +225,11 @@ def test_attention_band_persistent(gpu_device, monkeypatch, cus, B, H, KV, S, wi
     """Band layers with more units than CUs run attn_pw_kernel persistently (one workgroup per
     CU walking units blockIdx + k·grid as one KV-tile stream: the next unit's tiles staged during
     the current unit's last two, its Q loaded behind the last tile's barrier).  ACEHIP_ATTN_CUS
-    shrinks the grid so small shapes walk 2..10 units per workgroup (odd tile counts flip the
-    ring parity between units; ragged S leaves a partial last tile); cus = 0 keeps the real
-    CU count (the 240 s / 2- and 3-round shapes).  Bit-identical to one workgroup per unit."""
+    shrinks the grid: 32 units of 7 tiles on 16 CUs walk 2 units per workgroup (an odd tile count
+    flips the ring parity between units; ragged S leaves a partial last tile); cus = 0 keeps the
+    real CU count (the 240 s shape, 1.5 rounds, and its 3-round twin).  The rows with cus 37, 100
+    and 7 hold no more units (32, 56, 4) than CUs, so both arms run one workgroup per unit there.
+    Bit-identical to one workgroup per unit."""
     if cus:
         set_knob(monkeypatch, "ACEHIP_ATTN_CUS", str(cus))
     set_knob(monkeypatch, "ACEHIP_ATTN_PW", "2")
@@ -168,6 +241,10 @@ def test_attention_band_persistent(gpu_device, monkeypatch, cus, B, H, KV, S, wi
     outs = {}
     for pers in ("1", "0"):
         set_knob(monkeypatch, "ACEHIP_ATTN_PERSIST", pers)
+        units = (S + 127) // 128 * KV * B
+        walk = pers == "1" and (cus, B) in ((16, 2), (0, 2), (0, 4))     # the rows with more units than CUs
+        _assert_attn_route(ff, (B, H, KV, S, S, window), kernel=ff.ATTN_PW, units=units, nsplit=1,
+                           persist=int(walk), grid=(cus or 256) if walk else units)
         o = torch.full((B, S, H * 128), float("nan"), device=gpu_device, dtype=torch.bfloat16)
         ff.check(ff.lib().acehip_attention_bf16(ff.ptr(q), ff.ptr(k), ff.ptr(v), ff.ptr(o), B, H, KV, S, S,
                                                 window, 1 / math.sqrt(128), ff.stream_ptr()))
@@ -193,24 +270,65 @@ def _attn_ref(q, k, v, window):
     return torch.softmax(s, -1) @ v
 
 
+def _small(units, parts, **kw):
+    return dict(kernel=ATTN_SMALL, units=units, parts=parts, **kw)
+
+
+def _fwd(nrep, units, **kw):
+    return dict(kernel=ATTN_FWD, nrep=nrep, units=units, nsplit=1, streamk=0, grid=units, **kw)
+
+
+def _pw(units, **kw):
+    return dict(kernel=ATTN_PW, units=units, **{**dict(nsplit=1, persist=0, grid=units), **kw})
+
+
+# test_attention's routes on 256 CUs: one for both values of ACEHIP_ATTN_PW, or ("0", "7")
+_ATTENTION_ROUTES = {
+    (2, 4, 2, 300, 300, -1): _small(80, 2),
+    (2, 4, 2, 300, 300, 8): (_fwd(2, 12, unit_tiles=3), _pw(12, unit_tiles=3)),
+    (1, 16, 8, 1000, 1000, 128): (_fwd(2, 64, unit_tiles=7), _pw(64, unit_tiles=7)),
+    (2, 4, 2, 257, 641, -1): _small(72, 3),
+    (1, 2, 1, 50, 20, -1): _small(4, 1),
+    (1, 2, 1, 3000, 3000, 128): (_fwd(2, 24), _pw(24)),
+    (2, 16, 8, 3000, 3000, -1): (dict(kernel=ATTN_FWD, nrep=2, units=384, unit_tiles=47, streamk=1, grid=256),
+                                 _pw(384, full=256, nsplit=2, grid=512)),
+    (2, 16, 8, 3000, 3000, 128): (_fwd(1, 768, unit_tiles=7), _pw(384, persist=1, grid=256)),
+    (2, 16, 8, 3000, 641, -1): (_fwd(1, 768, unit_tiles=11), _pw(384, unit_tiles=11)),
+    (1, 16, 8, 125, 641, -1): _small(64, 3),
+    (1, 16, 8, 125, 125, 128): _small(64, 1, window=-1),
+    (2, 16, 8, 128, 128, -2): _small(128, 1, causal=1),
+    (1, 16, 8, 77, 77, -2): _small(48, 1, causal=1),
+    (3, 4, 2, 300, 300, -2): _small(120, 2, causal=1),
+    (1, 2, 2, 257, 257, -2): _small(18, 2, causal=1),
+}
+
+
 @pytest.mark.parametrize("B,H,KV,Sq,Sk,window", [(2, 4, 2, 300, 300, -1), (2, 4, 2, 300, 300, 8),
                                                   (1, 16, 8, 1000, 1000, 128), (2, 4, 2, 257, 641, -1),
                                                   (1, 2, 1, 50, 20, -1), (1, 2, 1, 3000, 3000, 128),
-                                                  # DiT shapes at 240 s: 384 units on 256 CUs → tail split (full),
-                                                  # GQA pair split into two 4-wave workgroups (band, cross)
+                                                  # DiT shapes at 240 s: 384 GQA-pair units on 256 CUs → stream-K
+                                                  # (full, "0") / tail split on attn_pw_kernel (full, "7"); band and
+                                                  # cross: the pair split into two 4-wave workgroups ("0"), the
+                                                  # persistent walk (band, "7"), whole units (cross, "7")
                                                   (2, 16, 8, 3000, 3000, -1), (2, 16, 8, 3000, 3000, 128),
                                                   (2, 16, 8, 3000, 641, -1),
-                                                  # 10 s song: 8 units → every unit KV-split
+                                                  # 10 s song (the band wider than the sequence is full attention):
+                                                  # 64 one-head units on attn_small_kernel
                                                   (1, 16, 8, 125, 641, -1), (1, 16, 8, 125, 125, 128),
-                                                  # causal: text encoder (128 tokens), ragged, nrep 1
+                                                  # causal: text encoder (128 tokens), ragged, one head per KV head —
+                                                  # attn_small_kernel's causal mode (attn_fwd_kernel's:
+                                                  # test_gpu_condenc.py test_causal_attention_small)
                                                   (2, 16, 8, 128, 128, -2), (1, 16, 8, 77, 77, -2),
                                                   (3, 4, 2, 300, 300, -2), (1, 2, 2, 257, 257, -2)])
 @pytest.mark.parametrize("pw", ["0", "7"])
 def test_attention(gpu_device, monkeypatch, B, H, KV, Sq, Sk, window, pw):
     """pw: ACEHIP_ATTN_PW — "0" every layer kind on attn_fwd_kernel, "7" the GQA-pair unmasked
-    kinds (full / band / cross) on the 64-row-per-wave attn_pw_kernel (production: band only)."""
+    kinds (full / band / cross) on the 64-row-per-wave attn_pw_kernel (production: band only).
+    Grids of at most 1.5 rounds of one-head × 32-row units run on attn_small_kernel under either."""
     set_knob(monkeypatch, "ACEHIP_ATTN_PW", pw)
     ff = _lib()
+    want = _ATTENTION_ROUTES[B, H, KV, Sq, Sk, window]
+    _assert_attn_route(ff, (B, H, KV, Sq, Sk, window), **(want if isinstance(want, dict) else want[pw == "7"]))
     g = torch.Generator(device="cpu").manual_seed(Sq * 7 + Sk)
     q = torch.randn(B, H, Sq, 128, generator=g).to(gpu_device, torch.bfloat16)
     k = torch.randn(B, KV, Sk, 128, generator=g).to(gpu_device, torch.bfloat16)
@@ -671,6 +789,8 @@ def test_graph_replay_single_streamk_layer(gpu_device, monkeypatch):
     from acehip.dit import DiTRuntime
     set_knob(monkeypatch, "ACEHIP_ATTN_CUS", "7")
     set_knob(monkeypatch, "ACEHIP_ATTN_STREAMK", "1")
+    _assert_attn_route(_lib(), (2, 2, 1, 1600, 1600, -1), kernel=ATTN_FWD, units=26, streamk=1, sk_total=26 * 25, grid=7)
+    _assert_attn_route(_lib(), (2, 2, 1, 1600, 1600, 8), kernel=ATTN_PW, streamk=0)
     cfg = DiTConfig.tiny(layers=2, window=8)
     W = {k: v.to(gpu_device, torch.bfloat16) for k, v in synth_dit_weights(cfg, seed=5, mode="parity").items()}
     g = torch.Generator().manual_seed(12)
@@ -981,15 +1101,22 @@ def test_attention_streamk(gpu_device, monkeypatch, cus, B, H, KV, Sq, Sk):
     """Stream-K rounds (ACEHIP_ATTN_STREAMK=1) for unmasked full / cross layers: the units' KV tiles
     as one sequence split evenly over the workgroups; a split unit's pieces meet through a
     last-arriver ticket and the folder folds them in workgroup order.  ACEHIP_ATTN_CUS shrinks the
-    grid so units span 2-3 workgroups; cus = 0 is the real 240 s full / cross shape; cus = 384 / 512
-    plan more workgroups than the device holds at once (advisor r05: the old flag spin needed the
-    whole grid resident) — no workgroup waits for another, so those must be exact too.  vs fp32,
-    and bit-identical across launches whichever piece folds."""
+    grid so units span 2-3 workgroups; cus = 0 is the real 240 s full shape and a 600 s one; cus = 512
+    plans more workgroups than the device holds at once (advisor r05: the old flag spin needed the
+    whole grid resident) — no workgroup waits for another, so that must be exact too.  On 384 CUs
+    the 384 units are one whole round: that row runs whole units on attn_fwd_kernel<2>, 1.5 to a
+    CU.  vs fp32, and bit-identical across launches whichever piece folds."""
     if cus:
         set_knob(monkeypatch, "ACEHIP_ATTN_CUS", str(cus))
     set_knob(monkeypatch, "ACEHIP_ATTN_STREAMK", "1")
     set_knob(monkeypatch, "ACEHIP_ATTN_PW", "2")
     ff = _lib()
+    units, tiles = (Sq + 127) // 128 * KV * B, (Sk + 63) // 64
+    if cus == 384:
+        _assert_attn_route(ff, (B, H, KV, Sq, Sk, -1), kernel=ATTN_FWD, nrep=2, units=384, nsplit=1, streamk=0, grid=384)
+    else:
+        _assert_attn_route(ff, (B, H, KV, Sq, Sk, -1), kernel=ATTN_FWD, nrep=2, units=units, streamk=1, sk_nt=tiles,
+                           sk_total=units * tiles, grid=cus or 256)
     g = torch.Generator(device="cpu").manual_seed(Sq + Sk + cus)
     q = torch.randn(B, H, Sq, 128, generator=g).to(gpu_device, torch.bfloat16)
     k = torch.randn(B, KV, Sk, 128, generator=g).to(gpu_device, torch.bfloat16)

@@ -42,11 +42,4 @@ for pw in ("0", "1"):
         else:
             os.environ.pop("ACEHIP_ATTN_CUS", None)
         print(json.dumps({"pw": pw, "case": name, "B": B, "plan_cus": cus or 256, "us": timeit(B, 3000)}), flush=True)
-        if name == "default_split":
-            for _ in range(3):
-                os.environ["ACEHIP_ATTN_DBG"] = "1"
-                a = timeit(B, 3000)
-                os.environ.pop("ACEHIP_ATTN_DBG")
-                b = timeit(B, 3000)
-                print(json.dumps({"pw": pw, "case": "no_handoff(wrong results) vs default", "us": [a, b]}), flush=True)
 os.environ.pop("ACEHIP_ATTN_CUS", None)
