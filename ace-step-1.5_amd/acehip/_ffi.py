@@ -40,6 +40,7 @@ EXPORTS = [
     "acehip_attention_decode_ws_bytes", "acehip_attention_decode_bf16", "acehip_lm_head_bf16",
     "acehip_lm_filter_ws_bytes", "acehip_lm_filter",
     "acehip_diag_pp_src_check", "acehip_diag_gemm_plan", "acehip_diag_attn_plan",
+    "acehip_diag_pp_lds_check", "acehip_diag_pp_slotimm",
 ]
 
 
@@ -140,6 +141,8 @@ def _declare(lib):
         "acehip_diag_pp_src_check": (c_int64, [c_int, c_int, c_int, c_int64, c_int64, c_int, c_int, c_int, c_int,
                                                POINTER(c_int), POINTER(c_int64), POINTER(c_int64),
                                                POINTER(c_int64)]),
+        "acehip_diag_pp_lds_check": (c_int64, [ctypes.c_uint32, POINTER(c_int64), POINTER(c_int), POINTER(c_int64)]),
+        "acehip_diag_pp_slotimm": (c_int, [c_int, c_int, c_int64, c_int64]),
         "acehip_diag_gemm_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int, ctypes.c_size_t, c_int, c_int,
                                           POINTER(GemmPlan)]),
         "acehip_diag_attn_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -831,7 +831,20 @@ constexpr int PP_SWIGLU_STORES = 256 / 2 / 16;
 // epilogue — 1: followed by exactly PP_SWIGLU_STORES stores per wave (vmcnt counts loads and
 // stores together, in order, so the counted wait leaves them and B(1) in flight), 0: by an
 // unknown number of stores (a ragged tile skips some), all waited for.
-template <int BM, int EPI, bool PERSIST, typename Src>
+//
+// SLOTIMM (ACEHIP_GEMM_SLOTIMM, scalar-base form only): the K loop is unrolled by the two ring
+// slots and peeled, so the read phase — which has to fit under the other wave group's MFMA
+// interval — holds no address arithmetic and no data-independent branch.  Every ds_read_b128 is
+// one of eight per-lane bases (operand × k-step × slot, formed before the loop; pp_addr.h
+// pp_rd_base) + the immediate 2048·sub-tile, the DMA destinations are the wave's scalar slot + a
+// constant, and A(kt+1) / B(kt+2) are staged unconditionally in the steady state of K-tile
+// pairs, which runs while more than three K-tiles are left; the last one to three run as
+// slot-constant bodies that keep the two stage predicates (fully constant tail bodies in an
+// if / else chain made the compiler copy the accumulators at the joins: scratch).  The same
+// reads, DMAs, waits, barriers and MFMAs in the same order as the loop below it, so the same
+// bits.  The asm reads are invisible to the compiler's lgkmcnt bookkeeping: the asm waits
+// before each barrier retire them.
+template <int BM, int EPI, bool PERSIST, bool SLOTIMM, typename Src>
 __device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src &src, f32x4 (&acc)[BM / 32][4],
                                         int slot, int pend) {
     constexpr int BN = 256, TM = BM / 2, SM = TM / 16, SMH = SM / 2;
@@ -901,31 +914,88 @@ __device__ __forceinline__ void pp_main(const GemmArgs &a, char *lds, const Src 
                     acc[h * SMH + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j][ks], xa[i][ks], acc[h * SMH + i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
     };
-    for (int kt = 0; kt < nk; ++kt) {
-        const char *b = lds + (kt & 1) * BUF;
-        // phase 0: B (all four sub-tiles, both k-steps) + A-half 0; A(kt+1) → other buffer
+    if constexpr (SLOTIMM) {
+        static_assert(Src::SCALAR, "the slot-immediate loop issues the scalar-base DMAs");
+        uint32_t ra[2][2], rb[2][2];   // [slot][ks]
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+        for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) bf[j][ks] = *(const bf16x8 *)(b + swz(brow + j * 16 + fr, ks * 4 + fc));
-        readA(b, 0);
-        if (kt + 1 < nk) stageA((kt + 1) & 1, (kt + 1) * BK);
-        wait_lgkm0();
-        bar();
-        mma(0);
-        bar();
-        // phase 1: A-half 1; B(kt+2) → this buffer's B slots (tile kt's B: last read by the
-        // other group in its phase 0, retired before the barrier above), then A(kt+1) landed
-        readA(b, 1);
-        if (kt + 2 < nk) {
-            stageB(kt & 1, (kt + 2) * BK);
-            wait_vm_lgkm0<NB>();
-        } else {
-            wait_vm_lgkm0<0>();
+            for (int ks = 0; ks < 2; ++ks) {
+                ra[s][ks] = pp_rd_base(lds_addr(lds), BM, arow, lane, ks, s);
+                rb[s][ks] = pp_rd_base(lds_addr(lds), BM, brow, lane, ks, s);
+                asm volatile("" : "+v"(ra[s][ks]), "+v"(rb[s][ks]));   // held, not rematerialised in the loop
+            }
+        // K-tile kt in ring slot S; sa / sb: A(kt+1) / B(kt+2) exist (compile-time true in the
+        // steady state, the parent's data-independent branches in the tail)
+        auto tile = [&](auto S_, auto STEADY_, int kt) {
+            constexpr int S = decltype(S_)::value;
+            constexpr bool STEADY = decltype(STEADY_)::value != 0;
+            sfor<0, 4>([&](auto j) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) bf[j][ks] = ds_read_b128_imm<pp_rd_imm(decltype(j)::value)>(rb[S][ks]);
+            });
+            sfor<0, SMH>([&](auto i) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) xa[i][ks] = ds_read_b128_imm<pp_rd_imm(decltype(i)::value)>(ra[S][ks]);
+            });
+            if (STEADY || kt + 1 < nk) stageA(S ^ 1, (kt + 1) * BK);
+            wait_lgkm0();
+            bar();
+            mma(0);
+            bar();
+            sfor<0, SMH>([&](auto i) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) xa[i][ks] = ds_read_b128_imm<pp_rd_imm(SMH + decltype(i)::value)>(ra[S][ks]);
+            });
+            if (STEADY || kt + 2 < nk) {
+                stageB(S, (kt + 2) * BK);
+                wait_vm_lgkm0<NB>();
+            } else {
+                wait_vm_lgkm0<0>();
+            }
+            bar();
+            mma(1);
+            bar();
+        };
+        constexpr IC<0> s0{}, tail{};
+        constexpr IC<1> s1{}, steady{};
+        int kt = 0;
+#pragma nounroll
+        for (; kt + 3 < nk; kt += 2) {
+            tile(s0, steady, kt);
+            tile(s1, steady, kt + 1);
         }
-        bar();
-        mma(1);
-        bar();
+        // one to three K-tiles are left (nk ≤ 3: all of them); kt is even
+        tile(s0, tail, kt);
+        if (kt + 1 < nk) tile(s1, tail, kt + 1);
+        if (kt + 2 < nk) tile(s0, tail, kt + 2);
+    } else {
+        for (int kt = 0; kt < nk; ++kt) {
+            const char *b = lds + (kt & 1) * BUF;
+            // phase 0: B (all four sub-tiles, both k-steps) + A-half 0; A(kt+1) → other buffer
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) bf[j][ks] = *(const bf16x8 *)(b + swz(brow + j * 16 + fr, ks * 4 + fc));
+            readA(b, 0);
+            if (kt + 1 < nk) stageA((kt + 1) & 1, (kt + 1) * BK);
+            wait_lgkm0();
+            bar();
+            mma(0);
+            bar();
+            // phase 1: A-half 1; B(kt+2) → this buffer's B slots (tile kt's B: last read by the
+            // other group in its phase 0, retired before the barrier above), then A(kt+1) landed
+            readA(b, 1);
+            if (kt + 2 < nk) {
+                stageB(kt & 1, (kt + 2) * BK);
+                wait_vm_lgkm0<NB>();
+            } else {
+                wait_vm_lgkm0<0>();
+            }
+            bar();
+            mma(1);
+            bar();
+        }
     }
     }
     if (wr == 0) bar();   // balance the barrier count: every wave's LDS reads have retired
@@ -978,7 +1048,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs &a, char *lds, const 
 // v_lshl_add_u64, a v_readfirstlane → m0 chain and a v_add_u32, in the read phase that has to
 // fit under the other wave group's MFMA interval).  The same addresses (pp_addr.h), so the same
 // bits; the host takes this form only where the 32-bit offsets cannot wrap (pp_saddr_fits).
-template <int BM, int EPI, bool SADDR>
+template <int BM, int EPI, bool SADDR, bool SLOTIMM = false>
 __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int bid) {
     GSTAMP(0);
     GSTAMP_REAL(4);
@@ -989,7 +1059,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
     std::conditional_t<SADDR, PPSrcOff<BM>, PPSrcPtr<BM>> src;
     src.set(a, m0, n0, wave, lane);
     f32x4 acc[BM / 32][4];
-    pp_main<BM, EPI, false>(a, lds, src, acc, blockIdx.x, -1);
+    pp_main<BM, EPI, false, SLOTIMM>(a, lds, src, acc, blockIdx.x, -1);
     pp_epilogue<BM, EPI>(a, lds, acc, m0, n0);
     if constexpr (EPI == EPI_HEADPOST) return;
 #ifdef GEMM_STAMPS
@@ -1013,7 +1083,7 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs &a, char *lds, int b
 // No workgroup waits for another and nothing is kept between launches.
 // The host guarantees ntot − nmain ≤ gridDim.x: a tail tile is its workgroup's last (a tail tile
 // followed by another would still be correct — its prologue is simply not issued early).
-template <int EPI>
+template <int EPI, bool SLOTIMM>
 __global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, GemmArgs t, int nmain, int ntot) {
     static_assert(EPI == EPI_SWIGLU, "the early prologue needs an epilogue that leaves LDS alone and a known store count");
     __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<256>()];
@@ -1032,7 +1102,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, Gem
     }
     for (; i < nmain; i += G) {
         f32x4 acc[8][4];
-        pp_main<256, EPI, true>(a, lds, src, acc, i, pend);
+        pp_main<256, EPI, true, SLOTIMM>(a, lds, src, acc, i, pend);
         const int cm0 = m0, cn0 = n0, nx = i + G;
         pend = cm0 + 256 <= a.M ? 1 : 0;   // a ragged tile's waves skip stores
         if (nx < ntot) {
@@ -1060,7 +1130,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, Gem
             tsrc.set(t, m0, n0, wave, lane);
         }
         f32x4 acc[4][4];
-        pp_main<128, EPI, true>(t, lds, tsrc, acc, i, pend);
+        pp_main<128, EPI, true, SLOTIMM>(t, lds, tsrc, acc, i, pend);
         pend = -1;
         pp_epilogue<128, EPI>(t, lds, acc, m0, n0);
 #ifdef GEMM_STAMPS
@@ -1075,21 +1145,21 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_persist_kernel(GemmArgs a, Gem
     }
 }
 
-template <int BM, int EPI, bool SADDR>
+template <int BM, int EPI, bool SADDR, bool SLOTIMM = false>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<BM>()];
-    gemm_pp_body<BM, EPI, SADDR>(a, lds, blockIdx.x);
+    gemm_pp_body<BM, EPI, SADDR, SLOTIMM>(a, lds, blockIdx.x);
 }
 
 // The tail-split GEMM (gemm_plan.h plan_tail_split: whole rounds of 256-row tiles + the remaining rows as
 // one round of 128-row tiles) in ONE launch: blocks [0, nmain) run the main grid, the rest the
 // tail grid, so the tail's blocks start on CUs as the main grid's last round drains instead of
 // behind a kernel boundary
-template <int EPI, bool SADDR>
+template <int EPI, bool SADDR, bool SLOTIMM = false>
 __global__ __launch_bounds__(512, 1) void gemm_pp_split_kernel(GemmArgs a, GemmArgs t, int nmain) {
     __shared__ __attribute__((aligned(16))) char lds[pp_lds_bytes<256>()];
-    if ((int)blockIdx.x < nmain) gemm_pp_body<256, EPI, SADDR>(a, lds, blockIdx.x);
-    else gemm_pp_body<128, EPI, SADDR>(t, lds, blockIdx.x - nmain);
+    if ((int)blockIdx.x < nmain) gemm_pp_body<256, EPI, SADDR, SLOTIMM>(a, lds, blockIdx.x);
+    else gemm_pp_body<128, EPI, SADDR, SLOTIMM>(t, lds, blockIdx.x - nmain);
 }
 
 // ---------------------------------------------------------------------------
@@ -1355,15 +1425,15 @@ int launch_w4(const GemmArgs &a, hipStream_t s) {
     return 0;
 }
 
-template <int BM, bool SADDR>
+template <int BM, bool SADDR, bool SLOTIMM = false>
 int launch_pp_as(const GemmArgs &a, hipStream_t s) {
     if (a.N % 256) return fail(-1, "gemm: N not a multiple of 256");
     const int tiles = ((a.M + BM - 1) / BM) * (a.N / 256);
     switch (a.epi) {
-        case EPI_STORE: gemm_pp_kernel<BM, EPI_STORE, SADDR><<<tiles, 512, 0, s>>>(a); break;
-        case EPI_GATED_RES: gemm_pp_kernel<BM, EPI_GATED_RES, SADDR><<<tiles, 512, 0, s>>>(a); break;
-        case EPI_RES: gemm_pp_kernel<BM, EPI_RES, SADDR><<<tiles, 512, 0, s>>>(a); break;
-        case EPI_SWIGLU: klaunch(gemm_pp_kernel<BM, EPI_SWIGLU, SADDR>, dim3(tiles), dim3(512), s, a); break;
+        case EPI_STORE: gemm_pp_kernel<BM, EPI_STORE, SADDR, SLOTIMM><<<tiles, 512, 0, s>>>(a); break;
+        case EPI_GATED_RES: gemm_pp_kernel<BM, EPI_GATED_RES, SADDR, SLOTIMM><<<tiles, 512, 0, s>>>(a); break;
+        case EPI_RES: gemm_pp_kernel<BM, EPI_RES, SADDR, SLOTIMM><<<tiles, 512, 0, s>>>(a); break;
+        case EPI_SWIGLU: klaunch(gemm_pp_kernel<BM, EPI_SWIGLU, SADDR, SLOTIMM>, dim3(tiles), dim3(512), s, a); break;
         case EPI_CONV:
             if constexpr (BM == 256 || BM == 128) {
                 gemm_pp_kernel<BM, EPI_CONV, false><<<tiles, 512, 0, s>>>(a);
@@ -1372,7 +1442,7 @@ int launch_pp_as(const GemmArgs &a, hipStream_t s) {
             return fail(-1, "gemm: the conv epilogue runs on the 256- or 128-row ping-pong tile");
         case EPI_HEADPOST:
             if constexpr (BM == 256 || BM == 192 || BM == 128) {
-                gemm_pp_kernel<BM, EPI_HEADPOST, false><<<tiles, 512, 0, s>>>(a);
+                gemm_pp_kernel<BM, EPI_HEADPOST, SLOTIMM, SLOTIMM><<<tiles, 512, 0, s>>>(a);   // scalar base only with slot immediates
                 break;
             }
             return fail(-1, "gemm: head-post epilogue needs the 256-, 192- or 128-row ping-pong tile");
@@ -1383,7 +1453,9 @@ int launch_pp_as(const GemmArgs &a, hipStream_t s) {
 }
 template <int BM>
 int launch_pp(const GemmArgs &a, hipStream_t s) {
-    return pp_tile_saddr(knobs().gemm_saddr, a.epi, BM, a.lda, a.ldw) ? launch_pp_as<BM, true>(a, s) : launch_pp_as<BM, false>(a, s);
+    const Knobs &k = knobs();
+    if (pp_tile_slotimm(k.gemm_slotimm, k.gemm_saddr, a.epi, BM, a.lda, a.ldw)) return launch_pp_as<BM, true, true>(a, s);
+    return pp_tile_saddr(k.gemm_saddr, a.epi, BM, a.lda, a.ldw) ? launch_pp_as<BM, true>(a, s) : launch_pp_as<BM, false>(a, s);
 }
 
 template <int BM, int BN, int WM, int WN, int STAGES, int NH = 0>
@@ -1516,7 +1588,10 @@ static int gemm_launch(const GemmArgs &a, const GemmPlan &p, hipStream_t s, RowA
         }
         case ACEHIP_ROUTE_WALK:   // gemm_pp_persist_kernel: at most one tail tile per workgroup
             if (p.ntail > p.grid) return fail(-1, "gemm: persistent walk with more tail tiles than workgroups");
-            klaunch(gemm_pp_persist_kernel<EPI_SWIGLU>, dim3(p.grid), dim3(512), s, hd, tl, p.nmain, p.nmain + p.ntail);
+            if (pp_tile_slotimm(knobs().gemm_slotimm, 1, a.epi, 256, a.lda, a.ldw))   // the walk is scalar-base under either ACEHIP_GEMM_SADDR
+                klaunch(gemm_pp_persist_kernel<EPI_SWIGLU, true>, dim3(p.grid), dim3(512), s, hd, tl, p.nmain, p.nmain + p.ntail);
+            else
+                klaunch(gemm_pp_persist_kernel<EPI_SWIGLU, false>, dim3(p.grid), dim3(512), s, hd, tl, p.nmain, p.nmain + p.ntail);
             break;
         case ACEHIP_ROUTE_SPLITK: {   // fp32 partials of p.splits K ranges, then their sum + the epilogue
             GemmArgs q = a;
@@ -1539,10 +1614,12 @@ static int gemm_launch(const GemmArgs &a, const GemmPlan &p, hipStream_t s, RowA
             return 0;
         }
         case ACEHIP_ROUTE_TAIL1: {   // gemm_pp_split_kernel by source-address form and epilogue
-            static const Kern2 split[2][3] = {
+            static const Kern2 split[3][3] = {
+                {gemm_pp_split_kernel<EPI_SWIGLU, true, true>, gemm_pp_split_kernel<EPI_HEADPOST, true, true>, gemm_pp_split_kernel<EPI_STORE, true, true>},
                 {gemm_pp_split_kernel<EPI_SWIGLU, true>, gemm_pp_split_kernel<EPI_HEADPOST, true>, gemm_pp_split_kernel<EPI_STORE, true>},
                 {gemm_pp_split_kernel<EPI_SWIGLU, false>, gemm_pp_split_kernel<EPI_HEADPOST, false>, gemm_pp_split_kernel<EPI_STORE, false>}};
-            const Kern2 k = split[p.saddr ? 0 : 1][a.epi == EPI_SWIGLU ? 0 : a.epi == EPI_HEADPOST ? 1 : 2];
+            const int form = !p.saddr ? 2 : pp_tile_slotimm(knobs().gemm_slotimm, 1, a.epi, 256, a.lda, a.ldw) ? 0 : 1;
+            const Kern2 k = split[form][a.epi == EPI_SWIGLU ? 0 : a.epi == EPI_HEADPOST ? 1 : 2];
             if (a.epi == EPI_SWIGLU) klaunch(k, dim3(p.grid), dim3(512), s, hd, tl, p.nmain);
             else k<<<p.grid, 512, 0, s>>>(hd, tl, p.nmain);
             break;
@@ -1694,4 +1771,45 @@ extern "C" int64_t acehip_diag_pp_src_check(int M, int N, int K, int64_t lda, in
     if (max_a) *max_a = hi_a;
     if (max_b) *max_b = hi_b;
     return bad;
+}
+
+// acehip_diag_pp_lds_check (include/acehip.h): every LDS read of the slot-immediate K loop as
+// the kernel forms it — pp_rd_base + pp_rd_imm, in 32-bit arithmetic — against the ring slot's
+// swizzled address
+extern "C" int64_t acehip_diag_pp_lds_check(uint32_t lds, int64_t *reads, int *max_imm, int64_t *max_end) {
+    using namespace acehip;
+    int64_t bad = 0, n = 0, end = 0;
+    int imm_hi = 0;
+    for (int BM : {64, 128, 192, 256}) {
+        const int SM = BM / 32;   // 16-row A sub-tiles per wave
+        for (int wave = 0; wave < 8; ++wave)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int slot = 0; slot < 2; ++slot)
+                    for (int ks = 0; ks < 2; ++ks)
+                        for (int op = 0; op < 2; ++op) {   // 0: A, 1: W
+                            const int first = op ? pp_rd_brow(BM, wave) : pp_rd_arow(BM, wave);
+                            const uint32_t base = pp_rd_base(lds, BM, first, lane, ks, slot);
+                            for (int sub = 0; sub < (op ? 4 : SM); ++sub) {
+                                const int imm = pp_rd_imm(sub), row = first + sub * 16 + (lane & 15);
+                                const uint32_t got = base + (uint32_t)imm;
+                                const uint32_t want = lds + (uint32_t)(slot * pp_buf_bytes(BM)) + pp_swz(row, ks * 4 + (lane >> 4));
+                                const int64_t rel = (int64_t)got - (int64_t)lds;   // inside the kernel's LDS array
+                                bad += got != want || imm < 0 || imm >= 65536 || rel < 0 || rel + 16 > 2 * (int64_t)pp_buf_bytes(BM) ||
+                                       row >= (op ? BM + 256 : BM);
+                                imm_hi = std::max(imm_hi, imm);
+                                end = std::max(end, rel + 16);
+                                ++n;
+                            }
+                        }
+    }
+    if (reads) *reads = n;
+    if (max_imm) *max_imm = imm_hi;
+    if (max_end) *max_end = end;
+    return bad;
+}
+
+// acehip_diag_pp_slotimm (include/acehip.h)
+extern "C" int acehip_diag_pp_slotimm(int epi, int BM, int64_t lda, int64_t ldw) {
+    const acehip::Knobs &k = acehip::knobs();
+    return acehip::pp_tile_slotimm(k.gemm_slotimm, k.gemm_saddr, epi, BM, lda, ldw) ? 1 : 0;
 }

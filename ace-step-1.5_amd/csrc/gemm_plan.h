@@ -53,9 +53,23 @@ inline int variant_bn(int v) { return v == 7 || v == 8 || v == 9 ? 256 : v == 16
 // The store / residual / SwiGLU epilogues and the fused main + tail launch (head-post included)
 // take it; the conv epilogue and the one-launch head-post grid (layer 0's deduplicated QKV) stay
 // on the pointer form — in the round-8 A/B they were ahead with it, but not by twice the
-// same-vs-same spread in every round, so they have no scalar-base instantiation.
+// same-vs-same spread in every round, so this switch alone leaves them there (the
+// head-post grid takes the scalar base together with the slot-immediate loop: pp_tile_slotimm).
 inline bool pp_tile_saddr(int gemm_saddr, int epi, int BM, int64_t lda, int64_t ldw) {
     return gemm_saddr && epi != EPI_HEADPOST && epi != EPI_CONV && pp_saddr_fits(BM, lda, ldw);
+}
+
+// Whether a ping-pong launch of BM-row tiles runs the slot-immediate K loop (pp_main SLOTIMM, a
+// scalar-base loop): ACEHIP_GEMM_SLOTIMM, on every launch that takes the scalar-base form — the
+// one-tile kernels of pp_tile_saddr, the fused main + tail launch (BM = 256, where the plan says
+// saddr) and the persistent walk (scalar-base under either ACEHIP_GEMM_SADDR: gemm_saddr = 1) —
+// and on the one-launch head-post grid (layer 0's deduplicated QKV), which takes the scalar base
+// only together with the slot immediates: that pair passed the round-11 A/B against the pointer
+// form, the scalar base alone had not in round 8.  The conv epilogue did not pass it
+// either way and has no such instantiation: the knob does nothing there.  With the knob 0 every
+// launch is the one pp_tile_saddr picks.
+inline bool pp_tile_slotimm(int gemm_slotimm, int gemm_saddr, int epi, int BM, int64_t lda, int64_t ldw) {
+    return gemm_slotimm && gemm_saddr && epi != EPI_CONV && pp_saddr_fits(BM, lda, ldw);
 }
 
 // Half-chip grids (M ≈ 3000: the conditional rows' cross-Q / cross-O): the four-wave

@@ -27,6 +27,7 @@ struct Knobs {
     int dit_graph = 0;        // ACEHIP_DIT_GRAPH: HIP-graph replay of the forward body
     int gemm_persist = 1;     // ACEHIP_GEMM_PERSIST: multi-round SwiGLU ping-pong grids (with their tail-split tail) as one persistent tile walk, 0: one tile per workgroup
     int gemm_saddr = 1;       // ACEHIP_GEMM_SADDR: one-tile ping-pong K loops (store / residual / SwiGLU epilogues, the fused main + tail launch) issue their LDS-DMAs from a scalar tile base + 32-bit lane offsets (where those fit), 0: a 64-bit pointer per piece and lane
+    int gemm_slotimm = 1;     // ACEHIP_GEMM_SLOTIMM: the scalar-base ping-pong K loops (one-tile kernels, fused main + tail launch, persistent walk) run unrolled by ring slot and peeled, every LDS read a hoisted per-lane base + an immediate, 0: the slot and swizzle arithmetic per K-tile
     int gemm_cus = 0;         // ACEHIP_GEMM_CUS: CU count the GEMM tile planner uses (0: the device's; tests plan multi-round grids at small shapes)
     int gemm_hp_tail = 1;     // ACEHIP_GEMM_HPTAIL: head-post GEMMs as a tail split (256-row main rounds + a 128-row tail round) where the cost model prefers it
     int convt = 1;            // ACEHIP_CONVT: 1 ConvTranspose (N % 256 == 0, padded input) as an implicit GEMM, 0 conv_gemm_kernel

@@ -39,6 +39,7 @@ Knobs read_env() {
     k.gemm_hp_tail = env_int("ACEHIP_GEMM_HPTAIL", 1);
     k.gemm_persist = env_int("ACEHIP_GEMM_PERSIST", 1);
     k.gemm_saddr = env_int("ACEHIP_GEMM_SADDR", 1);
+    k.gemm_slotimm = env_int("ACEHIP_GEMM_SLOTIMM", 1);
     k.gemm_cus = env_int("ACEHIP_GEMM_CUS", 0);
     k.convp = env_int("ACEHIP_CONVP", 1);
     k.ru7 = env_int("ACEHIP_RU7", 2);

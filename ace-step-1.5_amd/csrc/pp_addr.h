@@ -53,6 +53,24 @@ PP_HD bool pp_saddr_fits(int BM, int64_t lda, int64_t ldw) {
            63 * ldw * 2 + 112 < lim && 64 * ldw * 2 < lim;
 }
 
+// ---- the K loop's LDS reads (gemm.hip pp_main) ----
+// One K-tile's LDS image is BM A rows then 256 W rows of 128 bytes, XOR-swizzled by 16-byte
+// chunk; the ring holds two of them, pp_buf_bytes apart.
+PP_HD int pp_buf_bytes(int BM) { return (BM + 256) * 128; }
+PP_HD uint32_t pp_swz(int row, int chunk) { return (uint32_t)(row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4)); }
+// First A / W image row of a wave's fragments: wave group wr = wave / 4 owns BM / 2 A rows, wave
+// column wc = wave % 4 owns 64 W rows.  Both are multiples of 16.
+PP_HD int pp_rd_arow(int BM, int wave) { return (wave >> 2) * (BM / 2); }
+PP_HD int pp_rd_brow(int BM, int wave) { return BM + (wave & 3) * 64; }
+// Slot-immediate form (ACEHIP_GEMM_SLOTIMM): a lane reads row  first + 16·sub + (lane & 15),
+// chunk ks·4 + lane / 16.  Rows 16 apart share their swizzle, so the address is a per-lane base —
+// one per operand, k-step ks and ring slot, formed once before the K loop — plus the
+// instruction's immediate 2048·sub.
+PP_HD uint32_t pp_rd_base(uint32_t lds, int BM, int first_row, int lane, int ks, int slot) {
+    return lds + (uint32_t)(slot * pp_buf_bytes(BM) + first_row * 128) + pp_swz(lane & 15, ks * 4 + (lane >> 4));
+}
+PP_HD constexpr int pp_rd_imm(int sub) { return sub * 2048; }
+
 // EPI_CONV: the A-side K offset (elements) of K-tile k0 = tap·cin + c0 — input rows shifted by
 // conv_a0 + tap·dil (negative for the front halo rows)
 PP_HD int pp_conv_ko(int k0, int cin, int dil, int a0) {

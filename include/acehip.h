@@ -462,6 +462,23 @@ int64_t acehip_diag_pp_src_check(int M, int N, int K, int64_t lda, int64_t ldw, 
                                  int conv_dil, int conv_a0, int *fits, int64_t *min_a, int64_t *max_a,
                                  int64_t *max_b);
 
+/* Host-only check, for tests (no GPU call): the slot-immediate K loop of the ping-pong GEMM tiles
+ * (ACEHIP_GEMM_SLOTIMM) issues every LDS read as a per-lane base register, formed once before the
+ * loop per operand, k-step and ring slot, plus an instruction immediate of 2048 bytes per 16-row
+ * sub-tile.  With the kernel's LDS array at 32-bit LDS address lds, this walks BM in {64, 128,
+ * 192, 256} x wave x lane x ring slot x k-step x operand x sub-tile, forms base + immediate in
+ * 32-bit arithmetic as the kernel does, and returns the number of reads that differ from the
+ * swizzled address of their row and chunk in that slot, whose immediate does not fit the 16-bit
+ * offset field, or that leave the tile's LDS array.  *reads: reads walked; *max_imm: the largest
+ * immediate; *max_end: the highest byte past any read, relative to lds.  Any out pointer may be
+ * NULL. */
+int64_t acehip_diag_pp_lds_check(uint32_t lds, int64_t *reads, int *max_imm, int64_t *max_end);
+
+/* Host-only, for tests: whether a ping-pong launch of BM x 256 tiles with epilogue epi (0-4, 6: the
+ * implicit-GEMM convs) and these leading dimensions runs the slot-immediate K loop under the current
+ * ACEHIP_GEMM_SLOTIMM / ACEHIP_GEMM_SADDR (the persistent walk takes it under either SADDR value). */
+int acehip_diag_pp_slotimm(int epi, int BM, int64_t lda, int64_t ldw);
+
 /* The route acehip_gemm_bf16_ex(..., variant -1) and the runtimes' GEMMs take for a shape: the
  * value the library's dispatch plans before it launches (csrc/gemm_plan.h holds the rules).
  * Fields a route does not use are 0. */
@@ -482,7 +499,9 @@ typedef struct acehip_gemm_plan {
     int splits, kper;         /* split-K: splits of kper K-tiles (the last one may be shorter) */
     int bn, stages;           /* split-K: tile width (64 / 128) and operand ring depth */
     int deferred;             /* split-K: the residual epilogue is left to the consumer norm */
-    int saddr;                /* the ping-pong launches issue their LDS-DMAs in the scalar-base form */
+    int saddr;                /* the ping-pong launches issue their LDS-DMAs in the scalar-base form under
+                                 ACEHIP_GEMM_SADDR alone (the one-launch head-post grid: 0 — it takes that
+                                 form only with the slot-immediate loop, acehip_diag_pp_slotimm) */
     int helpers;              /* the tile runs with LDS-DMA helper waves */
 } acehip_gemm_plan;
 
