@@ -38,7 +38,7 @@ EXPORTS = [
     "acehip_attention_probs_bf16", "acehip_dit_forward_capture",
     "acehip_enc_kv_create", "acehip_enc_prefill", "acehip_enc_decode",
     "acehip_attention_decode_ws_bytes", "acehip_attention_decode_bf16", "acehip_lm_head_bf16",
-    "acehip_lm_filter_ws_bytes", "acehip_lm_filter",
+    "acehip_lm_filter_ws_bytes", "acehip_lm_filter", "acehip_lm_score_ws_bytes", "acehip_lm_score_bf16",
     "acehip_diag_pp_src_check", "acehip_diag_gemm_plan", "acehip_diag_attn_plan",
     "acehip_diag_pp_lds_check", "acehip_diag_pp_slotimm",
 ]
@@ -170,6 +170,8 @@ def _declare(lib):
         "acehip_lm_head_bf16": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
         "acehip_lm_filter_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
         "acehip_lm_filter": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, P, ctypes.c_size_t, P]),
+        "acehip_lm_score_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
+        "acehip_lm_score_bf16": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P, P, P, P, P, ctypes.c_size_t, P]),
         "acehip_fsq_quantize": (c_int, [P, c_int, c_int, POINTER(c_int), c_int, P, c_int, P, P]),
         "acehip_fsq_codes_from_indices": (c_int, [P, c_int, POINTER(c_int), c_int, P, c_int, P]),
         "acehip_rmsnorm_bf16": (c_int, [P, P, P, P, c_int64, c_int, P, c_int, c_int, c_float, c_int, P]),

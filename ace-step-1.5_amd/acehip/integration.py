@@ -47,10 +47,16 @@ Seams:
              ``_forward_pass`` (``llm_inference.py:416-438``).  :func:`install_lm` — a separate
              call on the ``LLMHandler``, :func:`install` does not touch it — replaces it with
              :class:`~acehip.lm.HipCausalLM` (prefill + one-token decode over a K/V cache in the
-             handle, vocabulary projection); the logits processors, sampling, ``generate()``
-             and scoring (``get_hf_model_for_scoring``) stay in torch.  With ``filters=True`` the
+             handle, vocabulary projection); the logits processors, sampling and ``generate()``
+             stay in torch.  With ``filters=True`` the
              handler's ``_apply_top_k_filter`` / ``_apply_top_p_filter`` (``:367-385``) are rebound
              to :class:`~acehip.lm.HipLogitFilters` (``acehip_lm_filter``).
+
+  * score  — ``acestep/core/scoring/lm_score.py``, the auto-score of every generated song:
+             :func:`install_lm_score` rebinds its ``_calculate_log_prob`` /
+             ``_calculate_topk_recall`` to :meth:`~acehip.lm.HipCausalLM.score` (one forward over
+             prompt + target, then ``acehip_lm_score_bf16``: per target token the log-probability
+             and the rank, without the ``[S, V]`` logits).
 
 Failure policy: by default an acehip error propagates (the request fails
 loudly, ``generate_music.py:181-190`` turns it into an error payload).  The
@@ -264,8 +270,10 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
 
     Nothing is changed — and the returned dict says why under ``"skipped"`` — when the
     handler's backend is not ``pt`` or the model's heads / kv_heads ratio is not 1 or 2 (the
-    4B LM).  ``get_hf_model_for_scoring`` is rebound to return the original module
-    (``core/scoring/lm_score.py`` needs logits at every position).  ``fallback=True``: an acehip
+    4B LM).  ``get_hf_model_for_scoring`` is rebound to return the original module: the
+    reference's own scoring functions (``core/scoring/lm_score.py``) call a model for logits at
+    every position, which :class:`~acehip.lm.HipCausalLM` does not serve — :func:`install_lm_score`
+    puts scoring on the HIP path and keeps this binding for its fallback.  ``fallback=True``: an acehip
     error in a call is logged and that call and the rest of the generation run on the original
     module, the policy of :func:`install`.  ``runtime``: an already built
     :class:`~acehip.lm.HipLMRuntime` (or, in the host tests, a stand-in) instead of one built
@@ -311,6 +319,101 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
             llm_handler._apply_top_p_filter = f.top_p
             out["filters"] = {"hip": f, "top_k": orig_k, "top_p": orig_p}
     return out
+
+
+def recall_from_ranks(ranks, topk: int = 10):
+    """``_calculate_topk_recall``'s result (``core/scoring/lm_score.py:201-232``) from the 1-based
+    rank of every target token: a hit at k iff rank <= k, ``recall_per_k[k] = hits / T``, and the
+    average over positions of ``1 - (rank - 1) / topk`` for the hits at k = topk (0 for a miss)."""
+    n = len(ranks)
+    recall_per_k = {k: sum(1 for r in ranks if r <= k) / n if n > 0 else 0.0 for k in range(1, topk + 1)}
+    position_scores = [1.0 - (r - 1) / topk for r in ranks if r <= topk]
+    position_scores += [0.0] * (n - len(position_scores))
+    return (sum(position_scores) / len(position_scores) if position_scores else 0.0), recall_per_k
+
+
+def install_lm_score(llm_handler, lm_score_module=None, fallback: bool = False) -> dict:
+    """Put the LM's scoring (``acestep/core/scoring/lm_score.py``) on libacehip: the module
+    attributes ``_calculate_log_prob`` and ``_calculate_topk_recall`` are rebound, which their
+    callers ``calculate_pmi_score_per_condition`` and ``_calculate_metadata_recall`` look up as
+    module globals at call time — no caller changes.  ``lm_score_module``: the module object
+    (None imports ``acestep.core.scoring.lm_score`` lazily).  Returns the two originals under
+    ``"original"``.
+
+    The replacements keep the reference's signatures and return types.  They repeat its
+    tokenisation (``:144-158``: the prompt alone for ``prompt_len``, the full text with
+    ``truncation=True``; an empty or fully truncated target returns ``-inf``, respectively
+    ``(0.0, {})``), run under ``llm_handler._load_model_context()`` and score with
+    ``llm_handler.llm.score`` (:meth:`acehip.lm.HipCausalLM.score`: one forward over the sequence
+    and the fused vocabulary projection ``acehip_lm_score_bf16``; no ``[S, V]`` logits, no copy of
+    them to the host).  When ``llm_handler.llm`` is not a :class:`~acehip.lm.HipCausalLM` (a handler
+    on which :func:`install_lm` skipped, or another handler than the one installed on) the
+    original function runs.  ``fallback=True``: an acehip ``RuntimeError`` in a call is logged and
+    that call runs on the original function — on the original module, which
+    ``get_hf_model_for_scoring`` still returns — the policy of :func:`install` and
+    :func:`install_lm`.
+
+    Two deliberate differences from the reference's numbers:
+
+    * the mean log-probability is the fp32 mean of fp32 per-token values (fp32 log-sum-exp over
+      the bf16 logits).  The reference's ``log_softmax`` output and its mean are rounded to bf16,
+      because its CPU logits are bf16 tensors; ours is the more accurate number;
+    * top-k membership is decided by the target's rank ``1 + n_greater + n_equal_lower``: equal
+      logits rank by lower token id first (the rule of ``acehip_lm_filter``).  ``torch.topk``'s
+      order among equal values is unspecified, and bf16 logits tie often.  The recall values are
+      the reference's formula on those ranks (:func:`recall_from_ranks`)."""
+    from .lm import HipCausalLM
+    if lm_score_module is None:
+        import acestep.core.scoring.lm_score as lm_score_module
+    orig_lp = lm_score_module._calculate_log_prob
+    orig_recall = lm_score_module._calculate_topk_recall
+
+    def _scored(handler, formatted_prompt, target_text):
+        """(logprob fp32 [T], rank int64 [T]) on the host, or None for an empty / truncated target."""
+        tokenizer = handler.llm_tokenizer
+        prompt_len = tokenizer(formatted_prompt, return_tensors="pt", add_special_tokens=True)["input_ids"].shape[1]
+        full = tokenizer(formatted_prompt + target_text, return_tensors="pt", padding=False, truncation=True,
+                         add_special_tokens=True).to(handler.device)
+        input_ids = full["input_ids"]
+        if input_ids.shape[1] <= prompt_len:
+            return None
+        with torch.no_grad():
+            with handler._load_model_context():
+                lp, rank = handler.llm.score(input_ids, prompt_len)
+        return lp.float().cpu(), rank.cpu()
+
+    def _calculate_log_prob(llm_handler, formatted_prompt, target_text, temperature=1.0):
+        if not isinstance(getattr(llm_handler, "llm", None), HipCausalLM):
+            return orig_lp(llm_handler, formatted_prompt, target_text, temperature)
+        try:
+            out = _scored(llm_handler, formatted_prompt, target_text)
+        except RuntimeError as e:
+            if not fallback:
+                raise
+            log.warning("acehip LM scoring failed (%s); this call runs on PyTorch", e)
+            return orig_lp(llm_handler, formatted_prompt, target_text, temperature)
+        if out is None:
+            return float("-inf")
+        return out[0].mean().item()
+
+    def _calculate_topk_recall(llm_handler, formatted_prompt, target_text, topk=10):
+        if not isinstance(getattr(llm_handler, "llm", None), HipCausalLM):
+            return orig_recall(llm_handler, formatted_prompt, target_text, topk)
+        try:
+            out = _scored(llm_handler, formatted_prompt, target_text)
+        except RuntimeError as e:
+            if not fallback:
+                raise
+            log.warning("acehip LM scoring failed (%s); this call runs on PyTorch", e)
+            return orig_recall(llm_handler, formatted_prompt, target_text, topk)
+        if out is None:
+            return 0.0, {}
+        return recall_from_ranks(out[1].tolist(), topk)
+
+    lm_score_module._calculate_log_prob = _calculate_log_prob
+    lm_score_module._calculate_topk_recall = _calculate_topk_recall
+    return {"original": {"_calculate_log_prob": orig_lp, "_calculate_topk_recall": orig_recall},
+            "log_prob": _calculate_log_prob, "topk_recall": _calculate_topk_recall}
 
 
 def hip_normalize_audio(audio_data: torch.Tensor, target_db: float = -1.0) -> torch.Tensor:

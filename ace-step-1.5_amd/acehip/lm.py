@@ -20,8 +20,14 @@ The FSM-constrained processor, repetition penalty, temperature and the multinomi
 torch, where the reference has them; so do top-k / top-p (``_apply_top_k_filter`` /
 ``_apply_top_p_filter``, ``:367-385``) unless ``install_lm(..., filters=True)`` rebinds them to
 :class:`HipLogitFilters` (``acehip_lm_filter``).  ``generate()`` (no CFG, no
-constrained decoding, ``:946``) and scoring (``core/scoring/lm_score.py`` needs logits at
-every position) stay on the wrapped module.
+constrained decoding, ``:946``) stays on the wrapped module.
+
+Scoring (``core/scoring/lm_score.py``: a teacher-forced pass over prompt + target, then the
+log-probability or the top-k membership of every target token) is :meth:`HipCausalLM.score`:
+one ``acehip_enc_forward`` over the sequence (every position's final-norm row; the K/V cache is
+not touched) and ``acehip_lm_score_bf16`` over the target rows, which never forms the
+``[S, V]`` logits.  :func:`acehip.integration.install_lm_score` rebinds the reference's two
+scoring functions to it.
 
 The prefill runs on the flash kernels, which take heads / kv_heads of 1 or 2: the 0.6B and
 1.7B LMs (16 / 8).  The 4B LM (32 / 8) stays on PyTorch.
@@ -100,6 +106,34 @@ class HipLMRuntime:
         check(lib().acehip_lm_head_bf16(ptr(h), D, ptr(self.w_head), ptr(y), V, B, V, D, stream_ptr()), "lm_head")
         return y
 
+    def forward_all(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, S, D] bf16 → the final-norm row of every position [B, S, D] (causal, no padding
+        mask).  Runs on the stack's activation workspace only: the K/V cache is not touched."""
+        return self.stack.forward(x, None)
+
+    def score_rows(self, h: torch.Tensor, targets: torch.Tensor):
+        """h [T, D] bf16 rows (row stride >= D, a multiple of 8), targets [T] →
+        (logprob fp32, lse fp32, n_greater int32, n_equal_lower int32), each [T]
+        (``acehip_lm_score_bf16``).  The workspace is allocated on first use and kept."""
+        if h.dim() != 2 or h.dtype != torch.bfloat16 or h.stride(1) != 1:
+            h = h.to(self.device, torch.bfloat16).contiguous()
+        T, D = h.shape
+        V = self.vocab
+        tg = targets.to(device=self.device, dtype=torch.int32).contiguous()
+        need = int(lib().acehip_lm_score_ws_bytes(T, V))
+        ws = getattr(self, "_score_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._score_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        lp = torch.empty(T, device=self.device, dtype=torch.float32)
+        lse = torch.empty(T, device=self.device, dtype=torch.float32)
+        ng = torch.empty(T, device=self.device, dtype=torch.int32)
+        ne = torch.empty(T, device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            check(lib().acehip_lm_score_bf16(ptr(h), h.stride(0), ptr(self.w_head), ptr(tg), T, V, D, ptr(lp),
+                                             ptr(lse), ptr(ng), ptr(ne), ptr(ws), ws.numel(), stream_ptr()), "lm_score")
+        self._keep_score = (h, tg)
+        return lp, lse, ng, ne
+
     def close(self):
         self.stack.close()
 
@@ -125,7 +159,8 @@ class HipCausalLM:
     """Drop-in for ``LLMHandler.llm`` on the ``pt`` backend (see the module docstring).
 
     ``runtime`` provides ``device``, ``max_batch``, ``capacity``, ``embed``, ``prefill``,
-    ``decode`` and ``lm_head`` (:class:`HipLMRuntime`; the host tests inject a stand-in)."""
+    ``decode`` and ``lm_head``, and for :meth:`score` ``forward_all`` and ``score_rows``
+    (:class:`HipLMRuntime`; the host tests inject a stand-in)."""
 
     def __init__(self, runtime, wrapped=None, fallback: bool = False):
         self.rt = runtime
@@ -257,6 +292,33 @@ class HipCausalLM:
             self._cache = None
         out = self.wrapped(input_ids=ids, attention_mask=mask, use_cache=use_cache, **kw)
         return CausalLMOutput(out.logits[:, -1:, :], getattr(out, "past_key_values", None))
+
+    # ------------------------------------------------------------------ scoring
+    def score(self, input_ids: torch.Tensor, prompt_len: int):
+        """Teacher-forced scoring of ``input_ids[0, prompt_len:]`` given what precedes each token
+        (``core/scoring/lm_score.py:160-171``): → (logprob fp32 [T], rank int64 [T]), T = S − prompt_len.
+
+        Row j is the target ``ids[prompt_len + j]`` under the distribution predicted at position
+        ``prompt_len − 1 + j``; ``rank`` is 1-based, equal logits ranked by lower token id first
+        (``1 + n_greater + n_equal_lower``).  The logits are those of a bf16 ``lm_head``
+        (fp32 accumulate, rounded to bf16); the log-sum-exp and the log-probabilities are fp32.
+        Nothing of a running generation is touched: not the K/V cache, the key mask, the
+        generation counter or the cache ticket."""
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("HipCausalLM.score: input_ids [1, S] is required")
+        S = input_ids.shape[1]
+        prompt_len = int(prompt_len)
+        if S > self.capacity:
+            raise ValueError(f"HipCausalLM.score: {S} tokens exceed the capacity {self.capacity}")
+        limit = getattr(self.rt, "prefill_tokens", None)
+        if limit is not None and S > limit:
+            raise ValueError(f"HipCausalLM.score: {S} tokens exceed the runtime's prefill_tokens {limit}")
+        if not 1 <= prompt_len < S:
+            raise ValueError(f"HipCausalLM.score: need 1 <= prompt_len < S (got prompt_len {prompt_len}, S {S})")
+        ids = input_ids.to(self.device)
+        h = self.rt.forward_all(self.rt.embed(ids))[0]
+        lp, _, ng, ne = self.rt.score_rows(h[prompt_len - 1:S - 1], ids[0, prompt_len:])
+        return lp, 1 + ng.to(torch.int64) + ne.to(torch.int64)
 
     # ------------------------------------------------------------------ pass-throughs
     @property

@@ -221,6 +221,12 @@ int lm_head(const bf16_t *x, int64_t ldx, const bf16_t *W, bf16_t *y, int64_t ld
 size_t lm_filter_ws_bytes(int B, int V);
 int lm_filter(void *logits, int dtype, int ld, int B, int V, int top_k, float top_p, void *ws, size_t ws_bytes,
               hipStream_t s);
+// teacher-forced scoring head (lm_score.hip): per row of x [T][ldx] the log-probability of
+// targets[r] under softmax(bf16(x·Wᵀ)), the log-sum-exp, and the counts of logits above the
+// target's / equal to it at a lower index; ws: lm_score_ws_bytes(T, V) bytes
+size_t lm_score_ws_bytes(int T, int V);
+int lm_score(const bf16_t *x, int64_t ldx, const bf16_t *W, const int32_t *targets, int T, int V, int K, float *logprob,
+             float *lse, int32_t *n_greater, int32_t *n_equal_lower, void *ws, size_t ws_bytes, hipStream_t s);
 
 // --------------------------------------------------------------- sampler ---
 // element type bf16 (f32 = false) or fp32 (the parity mode)

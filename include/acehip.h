@@ -620,6 +620,27 @@ size_t acehip_lm_filter_ws_bytes(int B, int V);
 int acehip_lm_filter(void *logits, int dtype, int ld, int B, int V, int top_k, float top_p, void *ws, size_t ws_bytes,
                      void *stream);
 
+/* Teacher-forced scoring head (acestep/core/scoring/lm_score.py: _calculate_log_prob,
+ * _calculate_topk_recall) without a [T, V] logits matrix.  With
+ * logit[r][n] = bf16(Σ_k x[r][k]·W[n][k]) (fp32 accumulate, rounded to bf16 as a bf16 lm_head
+ * does), per row r in [0, T):
+ *   lse[r]       = log Σ_n exp(logit[r][n])               (fp32, max-subtracted)
+ *   logprob[r]   = logit[r][target[r]] − lse[r]
+ *   n_greater[r] = #{n : logit[r][n] >  logit[r][target[r]]}
+ *   n_equal_lower[r] = #{n < target[r] : logit[r][n] == logit[r][target[r]]}
+ * so the target's rank is 1 + n_greater + n_equal_lower (equal values: lower index first, the
+ * rule of acehip_lm_filter).  x bf16 [T, ldx >= K], W bf16 [V, K], both 16-byte aligned; targets
+ * device int32 [T]; outputs device fp32 / int32 [T].  A target outside [0, V): nothing is read
+ * out of bounds, that row gets logprob = NaN and both counts −1 (its lse is still the row's).
+ * The same input gives the same bits on every call.  ws: device scratch of
+ * acehip_lm_score_ws_bytes(T, V) = (2·ceil(V/128) + 1)·T·4 bytes, 4-byte aligned.  Caller's
+ * stream, no allocation, no host sync.  ACEHIP_E_ARG (nothing launched): null pointer, T < 1 or
+ * T > 8192, V < 1 or V > 2^23, K % 64 != 0, ldx < K or ldx % 8 != 0, a smaller workspace. */
+size_t acehip_lm_score_ws_bytes(int T, int V);
+int acehip_lm_score_bf16(const void *x, int ldx, const void *W, const int32_t *targets, int T, int V, int K,
+                         float *logprob, float *lse, int32_t *n_greater, int32_t *n_equal_lower, void *ws,
+                         size_t ws_bytes, void *stream);
+
 /* Qwen3RMSNorm (+ AdaLN modulation when shift/scale are given) over rows of D
  * (transformers modeling_qwen3.py:59-64; reference base:499,530,1496):
  * out = bf16(bf16(bf16(w·bf16(x·rsqrt(mean x²+eps)))·bf16(1+scale[b])) + shift[b]),
