@@ -41,6 +41,8 @@ EXPORTS = [
     "acehip_lm_filter_ws_bytes", "acehip_lm_filter", "acehip_lm_score_ws_bytes", "acehip_lm_score_bf16",
     "acehip_diag_pp_src_check", "acehip_diag_gemm_plan", "acehip_diag_attn_plan",
     "acehip_diag_pp_lds_check", "acehip_diag_pp_slotimm",
+    "acehip_attention_extend_ws_bytes", "acehip_attention_extend_bf16", "acehip_diag_attn_extend_plan",
+    "acehip_enc_extend",
 ]
 
 
@@ -90,6 +92,12 @@ class AttnPlan(ctypes.Structure):
     """acehip_attn_plan (include/acehip.h)."""
     _fields_ = [(n, c_int) for n in ("kernel", "nrep", "window", "units", "unit_tiles", "full", "nsplit", "parts",
                                      "grid", "block", "persist", "streamk", "sk_nt", "sk_total", "causal", "uses_ws")]
+
+
+class AttnExtendPlan(ctypes.Structure):
+    """acehip_attn_extend_plan (include/acehip.h)."""
+    _fields_ = [(n, c_int) for n in ("unit_rows", "unit_queries", "qblocks", "units", "tiles", "parts",
+                                     "tiles_per_part", "grid", "block", "uses_ws")]
 
 
 _LIB = None
@@ -167,6 +175,12 @@ def _declare(lib):
         "acehip_attention_decode_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
         "acehip_attention_decode_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_float,
                                                  P, ctypes.c_size_t, P]),
+        "acehip_enc_extend": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+        "acehip_attention_extend_ws_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+        "acehip_attention_extend_bf16": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int,
+                                                 c_float, P, ctypes.c_size_t, P]),
+        "acehip_diag_attn_extend_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                 POINTER(AttnExtendPlan), POINTER(ctypes.c_size_t)]),
         "acehip_lm_head_bf16": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, P]),
         "acehip_lm_filter_ws_bytes": (ctypes.c_size_t, [c_int, c_int]),
         "acehip_lm_filter": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_float, P, ctypes.c_size_t, P]),
@@ -276,6 +290,17 @@ def attn_plan(B, H, KV, Sq, Sk, window=-1, masked=False, have_ws=True, device_cu
     check(lib().acehip_diag_attn_plan(B, H, KV, Sq, Sk, window, int(masked), int(have_ws), device_cus,
                                       ctypes.byref(out)), "diag_attn_plan")
     return {n: getattr(out, n) for n, _ in AttnPlan._fields_}
+
+
+def attn_extend_plan(B, H, KV, n, pos, have_ws=True, device_cus=0) -> dict:
+    """The launch acehip_attention_extend_bf16 gives a shape (acehip_diag_attn_extend_plan; host only), as a
+    dict of acehip_attn_extend_plan's fields plus ws_need, the bytes of partials that plan writes."""
+    out, need = AttnExtendPlan(), ctypes.c_size_t(0)
+    check(lib().acehip_diag_attn_extend_plan(B, H, KV, n, pos, int(have_ws), device_cus, ctypes.byref(out),
+                                             ctypes.byref(need)), "diag_attn_extend_plan")
+    d = {n_: getattr(out, n_) for n_, _ in AttnExtendPlan._fields_}
+    d["ws_need"] = need.value
+    return d
 
 
 def reload_knobs():

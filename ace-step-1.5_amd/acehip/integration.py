@@ -277,7 +277,11 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
     error in a call is logged and that call and the rest of the generation run on the original
     module, the policy of :func:`install`.  ``runtime``: an already built
     :class:`~acehip.lm.HipLMRuntime` (or, in the host tests, a stand-in) instead of one built
-    from the model's weights.
+    from the model's weights.  Further keywords go to :class:`~acehip.lm.HipLMRuntime`:
+    ``install_lm(handler, score_slots=2)`` adds two cache rows in which
+    :meth:`~acehip.lm.HipCausalLM.score` keeps a prompt's K/V between the scoring calls that share
+    it (two, because the conditional and the unconditional prompt alternate; 0.94 GB each at
+    capacity 8192), so that a call computes its target's rows only.
 
     ``filters=True`` (and the LM itself installed): the handler's ``_apply_top_k_filter`` and
     ``_apply_top_p_filter`` (``llm_inference.py:367-385``, called through ``self`` by every loop)
@@ -351,7 +355,8 @@ def install_lm_score(llm_handler, lm_score_module=None, fallback: bool = False) 
     original function runs.  ``fallback=True``: an acehip ``RuntimeError`` in a call is logged and
     that call runs on the original function — on the original module, which
     ``get_hf_model_for_scoring`` still returns — the policy of :func:`install` and
-    :func:`install_lm`.
+    :func:`install_lm`.  Prompt reuse needs nothing here: it is decided inside ``score`` by the
+    runtime's ``score_slots`` (``install_lm(handler, score_slots=2)``).
 
     Two deliberate differences from the reference's numbers:
 

@@ -27,7 +27,13 @@ log-probability or the top-k membership of every target token) is :meth:`HipCaus
 one ``acehip_enc_forward`` over the sequence (every position's final-norm row; the K/V cache is
 not touched) and ``acehip_lm_score_bf16`` over the target rows, which never forms the
 ``[S, V]`` logits.  :func:`acehip.integration.install_lm_score` rebinds the reference's two
-scoring functions to it.
+scoring functions to it.  On a runtime with ``score_slots`` the calls that share a prompt reuse
+its K/V: a slot is a cache row past the generation's, and a call runs ``acehip_enc_extend`` over
+the positions that follow the longest prefix a slot already holds.
+
+:meth:`HipCausalLM.extend` is the multi-token continuation of a running generation
+(``acehip_enc_extend``: n new tokens per sequence in one pass); ``__call__`` keeps the
+reference's one-token contract.
 
 The prefill runs on the flash kernels, which take heads / kv_heads of 1 or 2: the 0.6B and
 1.7B LMs (16 / 8).  The 4B LM (32 / 8) stays on PyTorch.
@@ -52,10 +58,15 @@ class HipLMRuntime:
     the embedding table and the ``lm_head`` weight."""
 
     def __init__(self, cfg: DiTConfig, device: int = 0, max_batch: int = 16, capacity: int = 8192,
-                 prefill_tokens: Optional[int] = None):
+                 prefill_tokens: Optional[int] = None, score_slots: int = 0):
         self.cfg = cfg
         self.device = torch.device("cuda", device)
         self.max_batch, self.capacity = max_batch, capacity
+        # cache rows [max_batch, max_batch + score_slots) belong to HipCausalLM.score's prompt reuse.
+        # One cache row is layers · kv_heads · capacity · 128 · 2 (K, V) · 2 bytes: 0.94 GB for
+        # either LM (28 layers, 8 KV heads) at capacity 8192
+        self.score_slots = int(score_slots)
+        self.cache_epoch = 0
         # prompt tokens of one prefill (B·S): the activation workspace is sized by it
         self.prefill_tokens = prefill_tokens or min(max_batch * capacity, 4 * capacity)
         self.stack = EncoderStack(cfg, cfg.num_hidden_layers, 0, device=device,
@@ -70,7 +81,14 @@ class HipLMRuntime:
         tied = lm_head is None or lm_head.data_ptr() == emb.data_ptr()
         self.w_head = self.table if tied else lm_head.detach().to(self.device, torch.bfloat16).contiguous()
         self.stack.load({k: v for k, v in weights.items() if k != "embed_tokens.weight"})
-        check(lib().acehip_enc_kv_create(self.stack.h, self.max_batch, self.capacity), "enc_kv_create")
+        check(lib().acehip_enc_kv_create(self.stack.h, self.max_batch + self.score_slots, self.capacity),
+              "enc_kv_create")
+        self.reset_score_cache()
+
+    def reset_score_cache(self):
+        """Whatever the scoring rows of the cache held is no longer valid: every
+        :class:`HipCausalLM` on this runtime empties its slots before its next ``score``."""
+        self.cache_epoch += 1
 
     @property
     def vocab(self) -> int:
@@ -96,6 +114,21 @@ class HipLMRuntime:
         ld = kmask.stride(0) if kmask is not None else 0
         check(lib().acehip_enc_decode(self.stack.h, ptr(x), ptr(kmask), ld, B, pos, ptr(out), stream_ptr()),
               "enc_decode")
+        self._keep = (x, kmask)
+        return out
+
+    def extend(self, x: torch.Tensor, kmask: Optional[torch.Tensor], row0: int, pos: int) -> torch.Tensor:
+        """x [B, n, D] bf16: n tokens per sequence appended at cache positions [pos, pos + n) of
+        cache rows row0 .. row0 + B − 1; kmask uint8 [rows, ld] over cache positions (row b for
+        sequence b) or None → the final-norm row of every new position [B, n, D]
+        (``acehip_enc_extend``)."""
+        x = x.contiguous()
+        B, n, D = x.shape
+        out = torch.empty(B, n, D, device=self.device, dtype=torch.bfloat16)
+        ld = kmask.stride(0) if kmask is not None else 0
+        with torch.cuda.device(self.device):
+            check(lib().acehip_enc_extend(self.stack.h, ptr(x), ptr(kmask), ld, row0, B, pos, n, ptr(out),
+                                          stream_ptr()), "enc_extend")
         self._keep = (x, kmask)
         return out
 
@@ -159,7 +192,8 @@ class HipCausalLM:
     """Drop-in for ``LLMHandler.llm`` on the ``pt`` backend (see the module docstring).
 
     ``runtime`` provides ``device``, ``max_batch``, ``capacity``, ``embed``, ``prefill``,
-    ``decode`` and ``lm_head``, and for :meth:`score` ``forward_all`` and ``score_rows``
+    ``decode`` and ``lm_head``, for :meth:`score` ``forward_all`` and ``score_rows``, and for
+    :meth:`extend` and the prompt-reusing :meth:`score` ``extend`` (and ``score_slots``)
     (:class:`HipLMRuntime`; the host tests inject a stand-in)."""
 
     def __init__(self, runtime, wrapped=None, fallback: bool = False):
@@ -176,6 +210,14 @@ class HipCausalLM:
         self._generation = 0
         self._cache: Optional[HipKVCache] = None
         self._delegating = False     # fallback: the rest of this generation runs on the wrapped module
+        # prompt-reusing scoring: slot s is cache row max_batch + s; _slot_ids[s] is the CPU id
+        # tensor whose K/V that row holds (None: empty), _slot_used[s] the call that last took it
+        self.score_slots = int(getattr(runtime, "score_slots", 0) or 0)
+        self._slot_ids = [None] * self.score_slots
+        self._slot_used = [0] * self.score_slots
+        self._slot_tick = 0
+        self._slot_epoch = getattr(runtime, "cache_epoch", 0)
+        self.score_stats = {"calls": 0, "tokens_computed": 0, "tokens_reused": 0, "last_start": None}
 
     @classmethod
     def from_reference_model(cls, model, max_batch: int = 16, capacity: int = 8192, fallback: bool = False,
@@ -282,19 +324,105 @@ class HipCausalLM:
         past.length = pos + 1
         return CausalLMOutput(logits, past)
 
-    def _fall_back(self, ids, mask, past, use_cache, kw):
+    def _fall_back(self, ids, mask, past, use_cache, kw, new: int = 1, keep: int = 1):
         """The failing call and the rest of this generation on the wrapped module: it is given
-        the whole sequence so far (prompt and every token fed since) and builds its own cache."""
+        the whole sequence so far (prompt and every token fed since, the `new` of this call
+        included) and builds its own cache; the logits of the last `keep` positions return."""
         self._delegating = True
         if past is not None:
-            B, n = past.batch, past.length + 1
+            B, n = past.batch, past.length + new
             ids = self._ids[:B, :n].to(ids.device)
             self._cache = None
         out = self.wrapped(input_ids=ids, attention_mask=mask, use_cache=use_cache, **kw)
-        return CausalLMOutput(out.logits[:, -1:, :], getattr(out, "past_key_values", None))
+        return CausalLMOutput(out.logits[:, -keep:, :], getattr(out, "past_key_values", None))
+
+    # ------------------------------------------------------------------ multi-token continuation
+    def extend(self, input_ids, past_key_values, attention_mask=None, logits: str = "last", **kw):
+        """``model(input_ids[B, n], past_key_values, attention_mask[B, past + n])``: n >= 1 new tokens
+        per sequence appended to a running generation in one pass (``acehip_enc_extend``).  The
+        ticket is checked as in ``__call__`` (foreign or stale cache, changed batch), the cache
+        must hold ``past.length + n`` positions and a mask, if given, is ``[B, past.length + n]``.
+        Returns logits ``[B, 1, V]`` of the last new position, or with ``logits="all"`` ``[B, n, V]``
+        of every new position, and the same ticket advanced by n.  ``__call__`` itself keeps
+        refusing more than one new token."""
+        if logits not in ("last", "all"):
+            raise ValueError("HipCausalLM.extend: logits must be 'last' or 'all'")
+        if input_ids is None or input_ids.dim() != 2 or input_ids.shape[1] < 1:
+            raise ValueError("HipCausalLM.extend: input_ids [B, n >= 1] is required")
+        n = input_ids.shape[1]
+        keep = n if logits == "all" else 1
+        if self._delegating and past_key_values is not None and not isinstance(past_key_values, HipKVCache):
+            out = self.wrapped(input_ids=input_ids, attention_mask=attention_mask,
+                               past_key_values=past_key_values, use_cache=True, **kw)
+            return CausalLMOutput(out.logits[:, -keep:, :], getattr(out, "past_key_values", None))
+        self._check_extend(input_ids, attention_mask, past_key_values)
+        try:
+            return self._extend(input_ids, attention_mask, past_key_values, keep)
+        except RuntimeError as e:
+            if not self.fallback:
+                raise
+            log.warning("acehip LM call failed (%s); this generation continues on PyTorch", e)
+            return self._fall_back(input_ids, attention_mask, past_key_values, True, kw, new=n, keep=keep)
+
+    def _check_extend(self, ids, mask, past):
+        if not isinstance(past, HipKVCache) or past._owner is not self:
+            raise ValueError("HipCausalLM: past_key_values is not a cache this model returned (foreign cache)")
+        if past is not self._cache or past._generation != self._generation:
+            raise ValueError("HipCausalLM: past_key_values is stale (a later prefill reset the cache)")
+        B, n = ids.shape
+        if B != past.batch:
+            raise ValueError(f"HipCausalLM: batch changed from {past.batch} to {B} within one generation")
+        if past.length + n > self.capacity:
+            raise ValueError(f"HipCausalLM: {past.length} cached + {n} new tokens exceed the K/V cache "
+                             f"(capacity {self.capacity})")
+        limit = getattr(self.rt, "prefill_tokens", None)
+        if limit is not None and B * n > max(limit, self.max_batch):
+            raise ValueError(f"HipCausalLM: [{B}, {n}] new tokens exceed the runtime's prefill_tokens {limit}")
+        if mask is not None and tuple(mask.shape) != (B, past.length + n):
+            raise ValueError(f"HipCausalLM: attention_mask {tuple(mask.shape)} must be [{B}, {past.length + n}]")
+
+    def _extend(self, ids, mask, past, keep):
+        B, pos = past.batch, past.length
+        n = ids.shape[1]
+        if mask is not None:
+            self._mask[:B, pos:pos + n] = (mask[:, -n:] != 0).to(device=self.device, dtype=torch.uint8)
+            self._masked = True
+        else:
+            self._mask[:B, pos:pos + n] = 1
+        if self._ids is not None:
+            self._ids[:B, pos:pos + n] = ids.to(self.device)
+        h = self.rt.extend(self.rt.embed(ids), self._mask if self._masked else None, 0, pos)   # [B, n, D]
+        rows = h[:, n - keep:].reshape(B * keep, h.shape[-1])
+        # lm_head takes at most 16 rows per call
+        out = torch.cat([self.rt.lm_head(rows[i:i + 16].contiguous()) for i in range(0, B * keep, 16)], 0)
+        past.length = pos + n
+        return CausalLMOutput(out.reshape(B, keep, -1), past)
 
     # ------------------------------------------------------------------ scoring
-    def score(self, input_ids: torch.Tensor, prompt_len: int):
+    def reset_score_cache(self):
+        """Empty every scoring slot: the next ``score`` of each starts from position 0."""
+        self._slot_ids = [None] * self.score_slots
+        self._slot_used = [0] * self.score_slots
+        self._slot_epoch = getattr(self.rt, "cache_epoch", 0)
+
+    def _take_slot(self, ids_cpu: torch.Tensor, prompt_len: int):
+        """(slot, start) for a sequence: the slot whose cached ids share the longest prefix p with
+        it (the least recently used among equals) and start = min(p, prompt_len − 1); without any
+        shared prefix the least recently used slot (an empty one first) and start 0.  One
+        refinement keeps two alternating prompts that share a template prefix apart: a match that
+        does not cover the prompt (p < prompt_len − 1) yields to an empty slot while there is one."""
+        def prefix(a):
+            m = min(a.numel(), ids_cpu.numel())
+            ne = (a[:m] != ids_cpu[:m]).nonzero()
+            return int(ne[0]) if ne.numel() else m
+        ps = [prefix(a) if a is not None else 0 for a in self._slot_ids]
+        lru = sorted(range(self.score_slots), key=lambda s: (self._slot_ids[s] is not None, self._slot_used[s], s))
+        best = max(lru, key=lambda s: ps[s])          # max keeps the first of equals: LRU order
+        if ps[best] == 0 or (ps[best] < prompt_len - 1 and self._slot_ids[lru[0]] is None):
+            return lru[0], 0
+        return best, min(ps[best], prompt_len - 1)
+
+    def score(self, input_ids: torch.Tensor, prompt_len: int, reuse: bool = True):
         """Teacher-forced scoring of ``input_ids[0, prompt_len:]`` given what precedes each token
         (``core/scoring/lm_score.py:160-171``): → (logprob fp32 [T], rank int64 [T]), T = S − prompt_len.
 
@@ -302,8 +430,15 @@ class HipCausalLM:
         ``prompt_len − 1 + j``; ``rank`` is 1-based, equal logits ranked by lower token id first
         (``1 + n_greater + n_equal_lower``).  The logits are those of a bf16 ``lm_head``
         (fp32 accumulate, rounded to bf16); the log-sum-exp and the log-probabilities are fp32.
-        Nothing of a running generation is touched: not the K/V cache, the key mask, the
-        generation counter or the cache ticket."""
+        Nothing of a running generation is touched: not its K/V cache rows, the key mask, the
+        generation counter or the cache ticket.
+
+        On a runtime with ``score_slots`` and with ``reuse`` the prompt's K/V is kept between
+        calls: each slot is a cache row past the generation's and remembers the ids it holds; a
+        call continues from the longest prefix a slot shares with it (``acehip_enc_extend`` over
+        positions [start, S) only) and leaves the whole sequence in that slot.  A failing call
+        leaves its slot empty.  ``score_stats`` counts calls and tokens computed / reused.
+        Without slots, or with ``reuse=False``, one ``acehip_enc_forward`` covers the sequence."""
         if input_ids is None or input_ids.dim() != 2 or input_ids.shape[0] != 1:
             raise ValueError("HipCausalLM.score: input_ids [1, S] is required")
         S = input_ids.shape[1]
@@ -316,8 +451,25 @@ class HipCausalLM:
         if not 1 <= prompt_len < S:
             raise ValueError(f"HipCausalLM.score: need 1 <= prompt_len < S (got prompt_len {prompt_len}, S {S})")
         ids = input_ids.to(self.device)
-        h = self.rt.forward_all(self.rt.embed(ids))[0]
-        lp, _, ng, ne = self.rt.score_rows(h[prompt_len - 1:S - 1], ids[0, prompt_len:])
+        if not (reuse and self.score_slots > 0):
+            h = self.rt.forward_all(self.rt.embed(ids))[0]
+            lp, _, ng, ne = self.rt.score_rows(h[prompt_len - 1:S - 1], ids[0, prompt_len:])
+            return lp, 1 + ng.to(torch.int64) + ne.to(torch.int64)
+        if self._slot_epoch != getattr(self.rt, "cache_epoch", 0):
+            self.reset_score_cache()
+        ids_cpu = input_ids[0].detach().to("cpu", torch.long)
+        slot, start = self._take_slot(ids_cpu, prompt_len)
+        self._slot_ids[slot] = None              # empty until the call has succeeded
+        self._slot_tick += 1
+        self._slot_used[slot] = self._slot_tick
+        h = self.rt.extend(self.rt.embed(ids[:, start:]), None, self.max_batch + slot, start)[0]
+        lp, _, ng, ne = self.rt.score_rows(h[prompt_len - 1 - start:S - 1 - start], ids[0, prompt_len:])
+        self._slot_ids[slot] = ids_cpu
+        st = self.score_stats                    # calls that succeeded
+        st["calls"] += 1
+        st["last_start"] = start
+        st["tokens_computed"] += S - start
+        st["tokens_reused"] += start
         return lp, 1 + ng.to(torch.int64) + ne.to(torch.int64)
 
     # ------------------------------------------------------------------ pass-throughs

@@ -186,4 +186,54 @@ inline AttnDecodePlan attn_decode_plan(int B, int KV, int n, bool have_ws, int c
     return {(steps + per - 1) / per, per};
 }
 
+// attention_extend (attn_extend.hip): n new queries per sequence at cache positions [pos, pos + n),
+// causal over the pos + n cached keys.  A unit is one workgroup's 128 stacked rows: the G = H / KV
+// query heads of one KV head × 128 / G consecutive queries, so a K/V tile is staged once per group;
+// units = B · KV · ⌈n / (128 / G)⌉, query block fastest.  Every unit's 64-key tiles [0, its last
+// diagonal] are cut into the same `parts` ranges of `tiles_per_part` tiles (the last unit holds all
+// `tiles` of them; an earlier unit's ranges past its diagonal hold no key and weigh 0 in the fold).
+// A grid of at least `cus` units is not split; a smaller one stops splitting where units × parts
+// would pass ONE round of the planned CUs (the kernel holds one workgroup per CU) and keeps at
+// least two tiles per part.  Measured at B = 1, 16 / 8 heads, one process (the CU knob moving the
+// plan): 64 new queries over 1500 keys 26.3 µs as 24 parts of one tile, 19.1 as 12 parts of two;
+// 512 over 1500 keys 47.1 µs as 8 parts (512 workgroups, two rounds), 32.6 as 4 parts (one round),
+// 44.9 unsplit; 512 over 8192 keys 90.7 / 76.1 / 214.  The rule also bounds the partials
+// (attn_extend_ws_bound): cus slabs of 128 rows × 132 floats, 17.3 MB at 256 CUs, whatever the shape.
+constexpr int EXTEND_ROWS = 128;            // stacked rows per unit: 4 waves × 32
+constexpr int EXTEND_MAX_PARTS = 64;
+constexpr int EXTEND_PART_STRIDE = 132;     // floats per (row, part): m, l, 2 pad, o[128] (16-B aligned)
+using AttnExtendPlan = acehip_attn_extend_plan;
+inline AttnExtendPlan attn_extend_plan(int B, int H, int KV, int n, int pos, bool have_ws, int cus) {
+    AttnExtendPlan p{};
+    const int G = H / KV;
+    p.unit_queries = EXTEND_ROWS / G;
+    p.unit_rows = EXTEND_ROWS;
+    p.qblocks = (n + p.unit_queries - 1) / p.unit_queries;
+    p.units = B * KV * p.qblocks;
+    p.tiles = (pos + n + ATTN_KT - 1) / ATTN_KT;
+    int parts = (int)std::min<int64_t>({(int64_t)(p.tiles + 1) / 2, std::max<int64_t>(1, (int64_t)cus / p.units),
+                                        (int64_t)EXTEND_MAX_PARTS});
+    if (!have_ws || p.units >= cus) parts = 1;      // a grid that fills the CUs runs whole units
+    p.tiles_per_part = (p.tiles + parts - 1) / parts;
+    p.parts = (p.tiles + p.tiles_per_part - 1) / p.tiles_per_part;
+    p.grid = p.units * p.parts;
+    p.block = 256;
+    p.uses_ws = p.parts > 1;
+    return p;
+}
+// bytes of partials a plan writes (0: one part, straight to o)
+inline size_t attn_extend_plan_ws_bytes(const AttnExtendPlan &p) {
+    return p.parts > 1 ? (size_t)p.grid * EXTEND_ROWS * EXTEND_PART_STRIDE * sizeof(float) : 0;
+}
+// the most any plan of (B, H, n) writes on `cus` CUs, over every pos and every G in {1, 2, 4}:
+// a split grid stays within cus workgroups
+inline size_t attn_extend_ws_bound(int B, int H, int n, int cus) {
+    int64_t units = 0;
+    for (int G = 1; G <= 4; G *= 2)
+        if (H % G == 0)
+            units = std::max<int64_t>(units, (int64_t)B * (H / G) * ((n + EXTEND_ROWS / G - 1) / (EXTEND_ROWS / G)));
+    const int64_t slabs = std::min<int64_t>((int64_t)cus, units * EXTEND_MAX_PARTS);
+    return (size_t)std::max<int64_t>(slabs, 1) * EXTEND_ROWS * EXTEND_PART_STRIDE * sizeof(float);
+}
+
 }  // namespace acehip

@@ -60,6 +60,9 @@ struct acehip_enc {
     bool kv_tried = false;     // a kv_create that failed part-way keeps its buffers until destroy: no second attempt
     void *dec_ws = nullptr;
     size_t dec_ws_bytes = 0;
+    // multi-token continuation (acehip_enc_extend): attn_extend's key-range partials
+    void *ext_ws = nullptr;
+    size_t ext_ws_bytes = 0;
 };
 
 // every GEMM of this runtime may use the handle's split-K workspace (small-M grids)
@@ -375,10 +378,12 @@ int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity) {
     h->dec_ws_bytes = attention_decode_ws_bytes(max_B, h->cfg.heads);
     bf16_t *kc = enc_alloc(h, per * h->L), *vc = kc ? enc_alloc(h, per * h->L) : nullptr;
     void *ws = vc ? enc_alloc(h, h->dec_ws_bytes / 2) : nullptr;
-    if (!ws) return fail(ACEHIP_E_OOM, "enc_kv_create: device allocation failed");   // freed by enc_destroy
+    h->ext_ws_bytes = attention_extend_ws_bytes(max_B, h->cfg.heads, h->cfg.max_tokens);
+    void *xws = ws ? enc_alloc(h, h->ext_ws_bytes / 2) : nullptr;
+    if (!xws) return fail(ACEHIP_E_OOM, "enc_kv_create: device allocation failed");   // freed by enc_destroy
     HIP_TRY(hipMemset(kc, 0, per * h->L * 2));
     HIP_TRY(hipMemset(vc, 0, per * h->L * 2));
-    h->Kc = kc; h->Vc = vc; h->dec_ws = ws;
+    h->Kc = kc; h->Vc = vc; h->dec_ws = ws; h->ext_ws = xws;
     h->kv_B = max_B; h->kv_cap = capacity;
     return 0;
 }
@@ -443,6 +448,67 @@ int acehip_enc_decode(acehip_enc *h, const void *x, const uint8_t *kmask, int ma
         RUN(hgemm(h, dn, s, &pend));
     }
     RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, 1, (bf16_t *)out, B, D, eps, s, pend));
+#undef RUN
+    return 0;
+}
+
+// n tokens per sequence appended at cache positions [pos, pos + n) of cache rows row0 .. row0 + B − 1:
+// acehip_enc_decode's layer loop on M = B·n rows — head-post writes q compact [B][H][n][128] and
+// k / v straight into the cache rows — with attention_extend in place of attention_decode
+int acehip_enc_extend(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int row0, int B, int pos, int n,
+                      void *out, void *stream) {
+    if (!h || !x || !out) return fail(ACEHIP_E_ARG, "null argument");
+    if (!h->finalized) return fail(ACEHIP_E_STATE, "enc_extend before finalize");
+    if (!h->Kc) return fail(ACEHIP_E_STATE, "enc_extend: no cache (acehip_enc_kv_create)");
+    if (B <= 0 || row0 < 0 || (int64_t)row0 + B > h->kv_B)
+        return fail(ACEHIP_E_ARG, "enc_extend: rows [row0, row0 + B) exceed the cache's batch");
+    if (pos < 0 || n < 1 || (int64_t)pos + n > h->kv_cap)
+        return fail(ACEHIP_E_ARG, "enc_extend: need pos >= 0, n >= 1, pos + n <= capacity");
+    if ((int64_t)B * n > h->cfg.max_tokens) return fail(ACEHIP_E_ARG, "enc_extend: B*n exceeds max_tokens");
+    if (kmask && mask_ld < pos + n) return fail(ACEHIP_E_ARG, "enc_extend: mask_ld < pos + n");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, cap = h->kv_cap, M = B * n;
+    const int H = h->cfg.heads, KV = h->cfg.kv_heads;
+    const float eps = h->cfg.eps, scale = 1.0f / sqrtf(128.0f);
+    const size_t per = (size_t)h->kv_B * KV * cap * 128, row_off = (size_t)row0 * KV * cap * 128;
+    int rc;
+#define RUN(e) do { if ((rc = (e))) return rc; } while (0)
+    HIP_TRY(hipMemcpyAsync(h->X, x, (size_t)M * D * 2, hipMemcpyDeviceToDevice, s));
+    RowAdd pend{};
+    for (int l = 0; l < h->L; ++l) {
+        const auto &ly = h->layers[l];
+        bf16_t *Kl = h->Kc + l * per + row_off, *Vl = h->Vc + l * per + row_off;
+        RUN(rmsnorm_mod(h->X, ly.ln1, nullptr, nullptr, 0, n, h->XN, M, D, eps, s, pend));
+        pend = RowAdd{};
+        // n rows per sequence: RoPE rows pos .. pos + n − 1, q compact, k / v into cache slots pos ..
+        GemmArgs q{};
+        q.A = h->XN; q.lda = D; q.W = ly.wqkv; q.ldw = D;
+        q.M = M; q.N = qd + 2 * kvd; q.K = D; q.epi = EPI_HEADPOST;
+        q.hp.B = B; q.hp.S = n; q.hp.nq = H; q.hp.nk = KV; q.hp.nv = KV; q.hp.qw = ly.qn; q.hp.kw = ly.kn;
+        q.hp.cos = h->rope_cos + (size_t)pos * 128; q.hp.sin = h->rope_sin + (size_t)pos * 128;
+        q.hp.q = h->Qh; q.hp.S_dst_q = n;
+        q.hp.k = Kl + (size_t)pos * 128; q.hp.v = Vl + (size_t)pos * 128;
+        q.hp.S_dst = cap; q.hp.eps = eps;
+        RUN(hgemm(h, q, s));
+        RUN(attention_extend(h->Qh, Kl, Vl, h->AO, B, H, KV, n, pos, cap, kmask, mask_ld, scale, h->ext_ws,
+                             h->ext_ws_bytes, s));
+        GemmArgs o{};
+        o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
+        o.M = M; o.N = D; o.K = qd; o.epi = EPI_RES; o.res = h->X; o.ldr = D;
+        RUN(hgemm(h, o, s, &pend));
+        RUN(rmsnorm_mod(h->X, ly.ln2, nullptr, nullptr, 0, n, h->XN, M, D, eps, s, pend));
+        pend = RowAdd{};
+        GemmArgs gu{};
+        gu.A = h->XN; gu.lda = D; gu.W = ly.wgu; gu.ldw = D; gu.C = h->Hb; gu.ldc = F;
+        gu.M = M; gu.N = 2 * F; gu.K = D; gu.epi = EPI_SWIGLU;
+        RUN(hgemm(h, gu, s));
+        GemmArgs dn{};
+        dn.A = h->Hb; dn.lda = F; dn.W = ly.wdown; dn.ldw = F; dn.C = h->X; dn.ldc = D;
+        dn.M = M; dn.N = D; dn.K = F; dn.epi = EPI_RES; dn.res = h->X; dn.ldr = D;
+        RUN(hgemm(h, dn, s, &pend));
+    }
+    RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, n, (bf16_t *)out, M, D, eps, s, pend));
 #undef RUN
     return 0;
 }

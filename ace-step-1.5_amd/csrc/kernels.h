@@ -214,6 +214,15 @@ size_t attention_decode_ws_bytes(int B, int H);
 int attention_decode(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int n,
                      int cap, const uint8_t *kmask, int mask_ld, float scale, void *ws, size_t ws_bytes,
                      hipStream_t s);
+// Causal attention of n new queries per sequence over a K/V cache (attn_extend.hip): q
+// [B][H][n][128], k / v [B][KV][cap][128] with rows [0, pos + n) valid, kmask [B][mask_ld] (1 =
+// attend) or null → o [B·n][H·128]; query i attends keys j <= pos + i.  H/KV in {1, 2, 4}.  ws:
+// attention_extend_ws_bytes(B, H, n) bytes (fp32 partials of the key ranges, folded in range
+// order; attn_plan.h attn_extend_plan) or null (one range per unit).
+size_t attention_extend_ws_bytes(int B, int H, int n);
+int attention_extend(const bf16_t *q, const bf16_t *k, const bf16_t *v, bf16_t *o, int B, int H, int KV, int n, int pos,
+                     int cap, const uint8_t *kmask, int mask_ld, float scale, void *ws, size_t ws_bytes,
+                     hipStream_t s);
 // y[m][n] = bf16(Σ_k x[m][k]·W[n][k]), M ≤ 16, any N (the LM's vocabulary projection)
 int lm_head(const bf16_t *x, int64_t ldx, const bf16_t *W, bf16_t *y, int64_t ldy, int M, int N, int K, hipStream_t s);
 // top-k / top-p logit filters of the token loop, in place (lm_filter.hip): logits [B][ld] of V

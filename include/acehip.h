@@ -278,6 +278,21 @@ int acehip_enc_prefill(acehip_enc *h, const void *x, const uint8_t *kmask, int B
  * ACEHIP_E_ARG when pos >= capacity.  Caller's stream, no allocation, no host sync. */
 int acehip_enc_decode(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int B, int pos, void *out,
                       void *stream);
+/* Multi-token continuation: model(input_ids[:, pos:pos+n], past_key_values, attention_mask
+ * [B, pos+n]) on cache rows row0 .. row0 + B - 1 (sequence b is cache row row0 + b).  x bf16
+ * [B, n, hidden]; the n tokens take cache indices and RoPE positions [pos, pos + n), each layer's
+ * K (normed, rotated) and V land in those cache rows, and every new query attends the cached
+ * keys j <= its own position (acehip_attention_extend_bf16).  kmask: device uint8
+ * [B, mask_ld >= pos + n] over cache positions, row b for sequence b, or NULL.  out bf16
+ * [B, n, hidden]: the final-norm row of every new position.  pos = 0 is a prefill that returns
+ * every row; n = 1 is a decode step on the other attention kernel.  The partials workspace was
+ * allocated by acehip_enc_kv_create (acehip_attention_extend_ws_bytes for cfg.max_tokens; 17.3 MB
+ * on 256 compute units).  Its size follows the CU count planned for at that time: with
+ * ACEHIP_ATTN_CUS raised afterwards a call whose plan needs more returns ACEHIP_E_ARG.  ACEHIP_E_STATE without a cache; ACEHIP_E_ARG unless row0 >= 0,
+ * row0 + B <= max_B, pos >= 0, n >= 1, pos + n <= capacity, B*n <= cfg.max_tokens and, with a
+ * mask, mask_ld >= pos + n.  Caller's stream, no allocation, no host sync. */
+int acehip_enc_extend(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int row0, int B, int pos,
+                      int n, void *out, void *stream);
 
 /* FSQ quantizer of the audio tokenizer (ResidualFSQ, 1 quantizer, levels
  * {8,8,8,5,5,5}: base:1196-1200; vector_quantize_pytorch FSQ restated, see
@@ -594,6 +609,41 @@ size_t acehip_attention_decode_ws_bytes(int B, int H);
 int acehip_attention_decode_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV, int n,
                                  int cap, const uint8_t *kmask, int mask_ld, float scale, void *ws, size_t ws_bytes,
                                  void *stream);
+
+/* Causal attention of n new queries per sequence over a K/V cache, head_dim 128, GQA with H/KV in
+ * {1, 2, 4} (the kernel behind acehip_enc_extend): q bf16 [B, H, n, 128]; k, v bf16
+ * [B, KV, cap, 128] of which rows [0, pos + n) are valid, the new tokens' rows [pos, pos + n)
+ * already in place; kmask uint8 [B, mask_ld >= pos + n] over cache positions (1 = attend) or NULL.
+ *   o[b·n + i][h·128 + :] = Σ_j softmax_j(scale · q[b,h,i] · k[b, h/(H/KV), j]) · v[b, h/(H/KV), j]
+ * over keys j <= pos + i with kmask[b][j] != 0; fp32 softmax, P rounded to bf16 before P·V as
+ * in acehip_attention_bf16.  Rows that are masked or at [pos + n, cap) are never used, whatever
+ * they hold; a query with no admissible key gives zeros (acehip_attention_decode_bf16's rules).
+ * ws: device scratch of acehip_attention_extend_ws_bytes(B, H, n) bytes, through which the key
+ * ranges of a small grid are folded in range order — no atomics: bit-identical results from call
+ * to call, at every split count — or NULL (one range per unit).  ACEHIP_E_ARG, nothing
+ * launched: a null q / k / v / o, B or n < 1, pos < 0, pos + n > cap, H/KV outside {1, 2, 4},
+ * mask_ld < pos + n with a mask, a workspace smaller than the plan needs. */
+size_t acehip_attention_extend_ws_bytes(int B, int H, int n);
+int acehip_attention_extend_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV, int n,
+                                 int pos, int cap, const uint8_t *kmask, int mask_ld, float scale, void *ws,
+                                 size_t ws_bytes, void *stream);
+
+/* The launch acehip_attention_extend_bf16 gives a shape (csrc/attn_plan.h attn_extend_plan). */
+typedef struct acehip_attn_extend_plan {
+    int unit_rows;            /* stacked rows per workgroup: the H/KV heads of a KV head x unit_queries queries */
+    int unit_queries;         /* 128 / (H/KV) */
+    int qblocks, units;       /* query blocks per sequence; units = B x KV x qblocks */
+    int tiles;                /* 64-key tiles of the pos + n keys (the last query block's loop) */
+    int parts, tiles_per_part;/* key ranges per unit and tiles per range; (parts - 1) x tiles_per_part < tiles */
+    int grid, block;          /* units x parts workgroups of 256 threads */
+    int uses_ws;              /* parts > 1: partials go through the workspace and a fold launch */
+} acehip_attn_extend_plan;
+/* Host-only, for tests (no kernel launch): the plan of that call with a workspace if have_ws, on
+ * device_cus compute units (0: the current device's; ACEHIP_ATTN_CUS replaces either), and in
+ * *ws_need (or NULL) the bytes of partials the plan writes.  Shapes the entry refuses return
+ * ACEHIP_E_ARG. */
+int acehip_diag_attn_extend_plan(int B, int H, int KV, int n, int pos, int have_ws, int device_cus,
+                                 acehip_attn_extend_plan *out, size_t *ws_need);
 
 /* Vocabulary projection of the token loop (lm_head of a bf16 Qwen3ForCausalLM):
  * y[m][n] = bf16(Σ_k x[m][k] · W[n][k]), fp32 accumulate; M <= 16, any N, K % 8 == 0,
