@@ -264,13 +264,18 @@ def install(handler, max_seconds: float = 600.0, max_batch: int = 8, fallback: b
 
 
 def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback: bool = False, runtime=None,
-               filters: bool = False, **kw) -> dict:
+               filters: bool = False, wide_gqa: bool = False, **kw) -> dict:
     """Put the 5 Hz LM's token loop on libacehip: ``llm_handler.llm`` (a transformers
     ``Qwen3ForCausalLM`` on the ``pt`` backend) becomes a :class:`~acehip.lm.HipCausalLM`.
 
     Nothing is changed — and the returned dict says why under ``"skipped"`` — when the
-    handler's backend is not ``pt`` or the model's heads / kv_heads ratio is not 1 or 2 (the
-    4B LM).  ``get_hf_model_for_scoring`` is rebound to return the original module: the
+    handler's backend is not ``pt`` or the model's heads / kv_heads ratio is not 1 or 2.
+    ``wide_gqa=True`` also installs a model of ratio 4 — the 4B LM, 32 / 8 heads — exactly like
+    the others (``filters``, ``score_slots``, ``fallback`` and ``runtime`` behave the same): its
+    prefill and its scoring forward run their attention on ``acehip_attention_extend_bf16``
+    instead of the flash kernels, which take ratios 1 and 2 only.  The switch is off by default,
+    so a ratio-4 model is skipped as before; any other ratio is skipped either way.
+    ``get_hf_model_for_scoring`` is rebound to return the original module: the
     reference's own scoring functions (``core/scoring/lm_score.py``) call a model for logits at
     every position, which :class:`~acehip.lm.HipCausalLM` does not serve — :func:`install_lm_score`
     puts scoring on the HIP path and keeps this binding for its fallback.  ``fallback=True``: an acehip
@@ -280,8 +285,10 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
     from the model's weights.  Further keywords go to :class:`~acehip.lm.HipLMRuntime`:
     ``install_lm(handler, score_slots=2)`` adds two cache rows in which
     :meth:`~acehip.lm.HipCausalLM.score` keeps a prompt's K/V between the scoring calls that share
-    it (two, because the conditional and the unconditional prompt alternate; 0.94 GB each at
-    capacity 8192), so that a call computes its target's rows only.
+    it (two, because the conditional and the unconditional prompt alternate), so that a call
+    computes its target's rows only.  A row is layers · kv_heads · capacity · 128 · 2 (K, V) · 2
+    bytes: at capacity 8192, 0.94 GB for the 0.6B and 1.7B LMs (28 layers) and 1.21 GB for the 4B
+    (36 layers).
 
     ``filters=True`` (and the LM itself installed): the handler's ``_apply_top_k_filter`` and
     ``_apply_top_p_filter`` (``llm_inference.py:367-385``, called through ``self`` by every loop)
@@ -301,9 +308,10 @@ def install_lm(llm_handler, capacity: int = 8192, max_batch: int = 16, fallback:
     orig = llm_handler.llm
     c = orig.config
     ratio = c.num_attention_heads / c.num_key_value_heads
-    if ratio not in (1, 2):
-        log.info("acehip install_lm: heads / kv_heads = %s (supported: 1, 2); the LM stays on PyTorch", ratio)
-        return {"lm": None, "skipped": f"heads / kv_heads = {ratio:g} (supported: 1 or 2)"}
+    supported = "1, 2 or 4" if wide_gqa else "1 or 2"
+    if ratio not in ((1, 2, 4) if wide_gqa else (1, 2)):
+        log.info("acehip install_lm: heads / kv_heads = %s (supported: %s); the LM stays on PyTorch", ratio, supported)
+        return {"lm": None, "skipped": f"heads / kv_heads = {ratio:g} (supported: {supported})"}
     if runtime is not None:
         lm = HipCausalLM(runtime, wrapped=orig, fallback=fallback)
     else:

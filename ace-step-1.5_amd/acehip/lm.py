@@ -35,8 +35,13 @@ the positions that follow the longest prefix a slot already holds.
 (``acehip_enc_extend``: n new tokens per sequence in one pass); ``__call__`` keeps the
 reference's one-token contract.
 
-The prefill runs on the flash kernels, which take heads / kv_heads of 1 or 2: the 0.6B and
-1.7B LMs (16 / 8).  The 4B LM (32 / 8) stays on PyTorch.
+The prefill of the 0.6B and 1.7B LMs (16 / 8 heads) runs on the flash kernels, which take
+heads / kv_heads of 1 or 2.  The 4B LM (32 / 8) is served too: the handle sends the attention of
+its prefill and of the scoring forward to ``acehip_attention_extend_bf16`` (every position a new
+query at ``pos = 0``), the one kernel besides the decode step's that stacks four query heads on a
+KV head.  That kernel writes a query row without any admissible key (the left padding) as zeros;
+nothing reads those rows.  :func:`acehip.integration.install_lm` installs a ratio-4 model only
+with ``wide_gqa=True``.
 """
 from __future__ import annotations
 
@@ -63,8 +68,9 @@ class HipLMRuntime:
         self.device = torch.device("cuda", device)
         self.max_batch, self.capacity = max_batch, capacity
         # cache rows [max_batch, max_batch + score_slots) belong to HipCausalLM.score's prompt reuse.
-        # One cache row is layers · kv_heads · capacity · 128 · 2 (K, V) · 2 bytes: 0.94 GB for
-        # either LM (28 layers, 8 KV heads) at capacity 8192
+        # One cache row is layers · kv_heads · capacity · 128 · 2 (K, V) · 2 bytes: at capacity 8192,
+        # 0.94 GB for the 0.6B and 1.7B LMs (28 layers, 8 KV heads) and 1.21 GB for the 4B (36 layers,
+        # 8 KV heads)
         self.score_slots = int(score_slots)
         self.cache_epoch = 0
         # prompt tokens of one prefill (B·S): the activation workspace is sized by it

@@ -20,7 +20,10 @@
 //
 // Runs once per song (twice in the reference, service_generate_execute.py:123
 // and base:1820), so it is launch-count-light rather than tuned: every GEMM
-// is the DiT's MFMA GEMM, every attention the DiT's flash kernel.
+// is the DiT's MFMA GEMM, every attention the DiT's flash kernel.  The one exception is a causal
+// stack with heads / kv_heads = 4 (the 4B language model): the flash kernels take ratios 1 and 2,
+// so its forward / prefill attention is attention_extend at pos = 0 over the head-post buffers
+// (enc_forward_impl), which writes a query row without any admissible key as zeros.
 #include <cmath>
 #include <map>
 #include <vector>
@@ -117,8 +120,18 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
     if (!cfg || !out) return fail(ACEHIP_E_ARG, "enc_create: null argument");
     if (cfg->head_dim != 128) return fail(ACEHIP_E_ARG, "enc_create: head_dim must be 128");
     if (cfg->hidden % 256 || cfg->intermediate % 64 || cfg->kv_heads <= 0 || cfg->heads % cfg->kv_heads ||
-        cfg->heads / cfg->kv_heads > 2 || ((cfg->heads + 2 * cfg->kv_heads) * 128) % 256)
+        (cfg->heads / cfg->kv_heads > 2 && cfg->heads / cfg->kv_heads != 4) ||
+        ((cfg->heads + 2 * cfg->kv_heads) * 128) % 256)
         return fail(ACEHIP_E_ARG, "enc_create: unsupported dims");
+    // heads / kv_heads == 4 (the 4B LM): attention_extend is the only kernel that stacks four
+    // query heads on a KV head, and it is causal — band and full layers, and the detokenizer's
+    // proj_out stack, have no kernel at that ratio
+    const bool wide = cfg->heads / cfg->kv_heads == 4;
+    if (wide) {
+        bool causal = cfg->sliding != nullptr && !cfg->out_dim;
+        for (int i = 0; causal && i < cfg->layers; ++i) causal = cfg->sliding[i] == 2;
+        if (!causal) return fail(ACEHIP_E_ARG, "enc_create: unsupported dims");
+    }
     if (cfg->in_dim < 0 || (cfg->in_dim && cfg->in_dim % 64) || cfg->out_dim < 0 || cfg->out_dim > 128 ||
         cfg->layers < 0 || cfg->max_tokens <= 0 || cfg->max_S <= 0)
         return fail(ACEHIP_E_ARG, "enc_create: in_dim % 64, out_dim <= 128, max_tokens/max_S > 0");
@@ -188,6 +201,11 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
         const size_t wb = attention_ws_bytes();
         h->attn_ws = enc_alloc(h, (wb + 1) / 2);
         ok = h->attn_ws && hipMemset(h->attn_ws, 0, wb) == hipSuccess;
+    }
+    if (ok && wide) {   // the forward's attention is attention_extend: its partials, cache or not
+        h->ext_ws_bytes = attention_extend_ws_bytes(cfg->max_tokens, cfg->heads, cfg->max_tokens);
+        h->ext_ws = enc_alloc(h, h->ext_ws_bytes / 2);
+        ok = h->ext_ws != nullptr;
     }
     if (!ok) {
         acehip_enc_destroy(h);
@@ -302,7 +320,12 @@ static int enc_forward_impl(acehip_enc *h, const void *x, const uint8_t *kmask, 
         }
         // layer kind: 0 full, 1 band |i−j| <= window, 2 causal (the Qwen3 text encoder)
         const int win = h->sliding[l] == 2 ? ATTN_CAUSAL : h->sliding[l] ? h->cfg.window : -1;
-        RUN(attention(h->Qh, h->Kh, h->Vh, h->AO, B, H, KV, S, S, win, scale, qd, h->attn_ws, s, kmask));
+        if (H / KV == 4)   // causal by enc_create; the flash kernels take ratios 1 and 2 only: the S
+                           // positions as S new queries over a "cache" of S rows, the head-post buffers
+            RUN(attention_extend(h->Qh, h->Kh, h->Vh, h->AO, B, H, KV, S, 0, S, kmask, S, scale, h->ext_ws,
+                                 h->ext_ws_bytes, s));
+        else
+            RUN(attention(h->Qh, h->Kh, h->Vh, h->AO, B, H, KV, S, S, win, scale, qd, h->attn_ws, s, kmask));
         GemmArgs o{};
         o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
         o.M = M; o.N = D; o.K = qd; o.epi = EPI_RES; o.res = h->X; o.ldr = D;
@@ -365,9 +388,9 @@ int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity) {
         return fail(ACEHIP_E_STATE, "enc_kv_create: an earlier attempt on this handle failed; destroy the handle "
                                     "(its partial buffers are freed there) and create a new one");
     const int G = h->cfg.heads / h->cfg.kv_heads;
-    if (G != 1 && G != 2)
-        return fail(ACEHIP_E_ARG, "enc_kv_create: heads/kv_heads must be 1 or 2 (the prefill's attention kernels); "
-                                  "this model stays on the PyTorch path");
+    if (G != 1 && G != 2 && G != 4)
+        return fail(ACEHIP_E_ARG, "enc_kv_create: heads/kv_heads must be 1, 2 or 4 (the attention kernels over "
+                                  "the cache); this model stays on the PyTorch path");
     if (!enc_all_causal(h) || h->cfg.out_dim)
         return fail(ACEHIP_E_ARG, "enc_kv_create: needs a causal stack (sliding[l] == 2 for every layer) without proj_out");
     if (max_B <= 0 || max_B > 65535 || max_B > h->cfg.max_tokens || capacity <= 0 || capacity > h->cfg.max_S)
@@ -378,8 +401,14 @@ int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity) {
     h->dec_ws_bytes = attention_decode_ws_bytes(max_B, h->cfg.heads);
     bf16_t *kc = enc_alloc(h, per * h->L), *vc = kc ? enc_alloc(h, per * h->L) : nullptr;
     void *ws = vc ? enc_alloc(h, h->dec_ws_bytes / 2) : nullptr;
-    h->ext_ws_bytes = attention_extend_ws_bytes(max_B, h->cfg.heads, h->cfg.max_tokens);
-    void *xws = ws ? enc_alloc(h, h->ext_ws_bytes / 2) : nullptr;
+    // a heads/kv_heads = 4 handle has had its extend workspace since enc_create, sized for
+    // max_tokens sequences: no smaller than this bound (max_B <= max_tokens)
+    void *xws = h->ext_ws;
+    if (!xws) {
+        h->ext_ws_bytes = attention_extend_ws_bytes(max_B, h->cfg.heads, h->cfg.max_tokens);
+        xws = ws ? enc_alloc(h, h->ext_ws_bytes / 2) : nullptr;
+    }
+    if (!ws) xws = nullptr;
     if (!xws) return fail(ACEHIP_E_OOM, "enc_kv_create: device allocation failed");   // freed by enc_destroy
     HIP_TRY(hipMemset(kc, 0, per * h->L * 2));
     HIP_TRY(hipMemset(vc, 0, per * h->L * 2));

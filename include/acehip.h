@@ -235,6 +235,18 @@ typedef struct acehip_enc_cfg {
 
 typedef struct acehip_enc acehip_enc;
 
+/* heads / kv_heads is 1 or 2 for any stack.  A ratio of 4 (the 4B language model, 32 / 8 heads) is
+ * accepted for a causal stack only — sliding given and sliding[l] == 2 for every layer, out_dim
+ * == 0: such a handle sends the attention of acehip_enc_forward / acehip_enc_prefill to
+ * acehip_attention_extend_bf16 (the S positions as S new queries at pos = 0 over the head-post
+ * buffers, cap = S), the one kernel besides the decode step's that stacks four query heads on a
+ * KV head, and allocates that kernel's partials workspace here
+ * (acehip_attention_extend_ws_bytes for cfg.max_tokens).  Band and full layers have no kernel
+ * at that ratio: any other ratio-4 stack, and any other ratio, is ACEHIP_E_ARG ("unsupported
+ * dims").  One difference follows from that kernel's rule: with a key mask, a query row without
+ * any admissible key (the left padding of a batch) leaves the attention as zeros, where the flash
+ * kernels give it a uniform average; such rows' outputs are never read, and their K / V stay
+ * masked for every later query. */
 int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out);
 /* Names relative to the module, as in its state dict: "embed_tokens.weight",
  * "layers.3.self_attn.q_proj.weight", "layers.3.input_layernorm.weight",
@@ -260,15 +272,19 @@ int acehip_enc_destroy(acehip_enc *h);
  * acehip_enc_kv_create allocates, once, the per-layer K / V caches
  * [layers][max_B][kv_heads][capacity][128] and the partials workspace of the decode
  * attention; acehip_enc_destroy frees them.  capacity <= cfg.max_S (the RoPE table),
- * max_B <= cfg.max_tokens.  heads / kv_heads must be 1 or 2 (the prefill runs on the flash
- * kernels): the 0.6B and 1.7B LMs; ACEHIP_E_ARG otherwise. */
+ * max_B <= cfg.max_tokens.  heads / kv_heads is 1, 2 (the 0.6B and 1.7B LMs; the prefill runs on
+ * the flash kernels) or 4 (the 4B LM; the prefill's attention is acehip_attention_extend_bf16, see
+ * acehip_enc_create, and the handle keeps the extend workspace it allocated there);
+ * ACEHIP_E_ARG otherwise. */
 int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity);
 /* First call of a generation: model(input_ids[B,S], attention_mask[B,S], use_cache=True).
  * The layer loop of acehip_enc_forward, causal AND key-padded when kmask (device uint8
  * [B, S], 1 = attend; the batch is left-padded) is given; each layer's K (after norm and
  * RoPE) and V of positions [0, S) also land in the cache; out bf16 [B, hidden] is the
  * final-norm row of position S - 1 of every sequence.  B <= max_B, S <= capacity,
- * B*S <= cfg.max_tokens.  Rows at padded positions stay finite. */
+ * B*S <= cfg.max_tokens.  Rows at padded positions stay finite (heads / kv_heads = 4: their
+ * attention output is exactly zero, acehip_enc_create).  At that ratio the K / V of the prompt
+ * are copied into the cache as at the others, and the attention reads the head-post buffers. */
 int acehip_enc_prefill(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream);
 /* Every later call: model(input_ids[:, -1:], past_key_values, attention_mask[B, pos+1]).
  * x bf16 [B, hidden], one token per sequence at cache index pos = the number of positions

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""One decode step of the 5 Hz LM on the HIP path, at the 0.6B and 1.7B shapes (28 layers,
-vocabulary 217 204 = Qwen3's 151 936 plus the audio-code tokens, synthetic weights), B = 2
+"""One decode step of the 5 Hz LM on the HIP path, at the 0.6B and 1.7B shapes (28 layers, 16 / 8
+heads) and, with --models 4B, at the 4B's (36 layers, 2560 / 9728, 32 / 8 heads) —
+vocabulary 217 204 = Qwen3's 151 936 plus the audio-code tokens, synthetic weights —, B = 2
 (CFG: cond + uncond row, the second left-padded), contexts 256 / 1024 / 2304 (the codes
 phase of a 240 s song ends near 2304).
 
@@ -20,9 +21,10 @@ the 256 MB last-level cache by itself, so its figure is an HBM figure.  attn_dec
 28 distinct caches as the layer loop does: 528 MB at context 2304 (from HBM), but 59 MB and
 235 MB at 256 and 1024, which fit in the last-level cache (the 300 MB write runs once per
 round, not per launch) — those two GB/s figures are not HBM figures.
-Writes profiles/lm_decode_bench.json.  Condition: call_ms <= hf_call_ms at every shape.
+Writes profiles/lm_decode_bench.json; a run of some models replaces those models' entries of an
+existing file and keeps the others.  Condition: call_ms <= hf_call_ms at every shape.
 
-usage: bench_lm_decode.py [--out PATH] [--rounds N] [--iters N] [--models 0.6B,1.7B]
+usage: bench_lm_decode.py [--out PATH] [--rounds N] [--iters N] [--models 0.6B,1.7B,4B]
 """
 import argparse
 import json
@@ -39,9 +41,10 @@ from acehip.config import DiTConfig  # noqa: E402
 from acehip.lm import HipCausalLM, HipLMRuntime  # noqa: E402
 from acehip.weights import synth_text_encoder_weights  # noqa: E402
 
-VOCAB, LAYERS, B, PAD = 217204, 28, 2, 9
+VOCAB, B, PAD = 217204, 2, 9
 CONTEXTS = (256, 1024, 2304)
-MODELS = {"0.6B": (1024, 3072), "1.7B": (2048, 6144)}
+# name -> (hidden, intermediate, layers, heads, kv_heads)
+MODELS = {"0.6B": (1024, 3072, 28, 16, 8), "1.7B": (2048, 6144, 28, 16, 8), "4B": (2560, 9728, 36, 32, 8)}
 HBM_BPS = 8e12
 
 
@@ -69,13 +72,13 @@ def interleaved(runs, rounds, iters, flush):
             {k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()})
 
 
-def hf_model(hidden, inter, dev):
+def hf_model(hidden, inter, LAYERS, H, KV, dev):
     try:
         from transformers import Qwen3Config, Qwen3ForCausalLM
     except Exception as e:                       # not installed: no baseline, said so in the JSON
         return None, f"transformers does not import: {e}"
     cfg = Qwen3Config(vocab_size=VOCAB, hidden_size=hidden, intermediate_size=inter, num_hidden_layers=LAYERS,
-                      num_attention_heads=16, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6,
+                      num_attention_heads=H, num_key_value_heads=KV, head_dim=128, rms_norm_eps=1e-6,
                       rope_theta=1_000_000.0, max_position_embeddings=8192, attention_bias=False,
                       use_sliding_window=False, tie_word_embeddings=True)
     with torch.device(dev):
@@ -96,12 +99,12 @@ def main():
     cap = max(CONTEXTS) + 64
     g = torch.Generator(device=dev).manual_seed(0)
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "iters": args.iters, "vocab": VOCAB,
-           "layers": LAYERS, "B": B, "left_pad_row1": PAD, "hbm_TBps_for_floor": HBM_BPS / 1e12, "models": {}}
+           "B": B, "left_pad_row1": PAD, "hbm_TBps_for_floor": HBM_BPS / 1e12, "models": {}}
     ok = True
     for name in args.models.split(","):
-        hidden, inter = MODELS[name]
+        hidden, inter, LAYERS, H, KV = MODELS[name]
         cfg = DiTConfig(hidden_size=hidden, intermediate_size=inter, num_hidden_layers=LAYERS,
-                        num_attention_heads=16, num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6,
+                        num_attention_heads=H, num_key_value_heads=KV, head_dim=128, rms_norm_eps=1e-6,
                         rope_theta=1_000_000.0)
         W = synth_text_encoder_weights(cfg, VOCAB, seed=0, mode="bench", device=dev, dtype=torch.bfloat16,
                                        backend="torch")
@@ -109,9 +112,9 @@ def main():
         rt.load(W)
         del W
         lm = HipCausalLM(rt)
-        layer_bytes = LAYERS * 2 * (hidden * (16 + 16) * 128 + hidden * 16 * 128 + 3 * hidden * inter)
+        layer_bytes = LAYERS * 2 * (hidden * (H + 2 * KV) * 128 + hidden * H * 128 + 3 * hidden * inter)
         head_bytes = 2 * VOCAB * hidden
-        hf, why = hf_model(hidden, inter, dev)
+        hf, why = hf_model(hidden, inter, LAYERS, H, KV, dev)
         rows = {}
         for ctx in CONTEXTS:
             ids = torch.randint(0, VOCAB, (B, ctx - 1), device=dev, generator=g)
@@ -142,7 +145,7 @@ def main():
                         hf(input_ids=tok, past_key_values=hf_past, attention_mask=full[:, :n + 1], use_cache=True)
                 runs["hf_call_ms"] = hf_call
             med, spread = interleaved(runs, args.rounds, args.iters, flush)
-            kv_bytes = LAYERS * B * 8 * ctx * 128 * 2 * 2
+            kv_bytes = LAYERS * B * KV * ctx * 128 * 2 * 2
             row = dict(med, spread_ms=spread, floor_ms=round((layer_bytes + head_bytes + kv_bytes) / HBM_BPS * 1e3, 4),
                        bytes={"layers": layer_bytes, "lm_head": head_bytes, "kv": kv_bytes})
             row["step_over_floor"] = round(row["step_ms"] / row["floor_ms"], 2)
@@ -164,12 +167,12 @@ def main():
                                                   hidden, ff.stream_ptr()), "lm_head")
         med, _ = interleaved({"lm_head": head}, args.rounds, args.iters, flush)
         kern["lm_head"] = {"us": round(med["lm_head"] * 1e3, 1), "GBps": round(head_bytes / med["lm_head"] * 1e-6, 1)}
-        nb = ff.lib().acehip_attention_decode_ws_bytes(B, 16)
+        nb = ff.lib().acehip_attention_decode_ws_bytes(B, H)
         ws = torch.empty(nb, device=dev, dtype=torch.uint8)
-        q = torch.randn(B, 16, 128, device=dev, generator=g).bfloat16()
-        o = torch.empty(B, 16 * 128, device=dev, dtype=torch.bfloat16)
+        q = torch.randn(B, H, 128, device=dev, generator=g).bfloat16()
+        o = torch.empty(B, H * 128, device=dev, dtype=torch.bfloat16)
         for ctx in CONTEXTS:
-            kc = torch.randn(LAYERS, 2, B, 8, ctx, 128, device=dev, generator=g).bfloat16()
+            kc = torch.randn(LAYERS, 2, B, KV, ctx, 128, device=dev, generator=g).bfloat16()
             km = torch.ones(B, ctx, dtype=torch.uint8, device=dev)
             km[1, :PAD] = 0
             state = {"l": 0}
@@ -177,21 +180,27 @@ def main():
             def attn():
                 l = state["l"] = (state["l"] + 1) % LAYERS
                 ff.check(ff.lib().acehip_attention_decode_bf16(ff.ptr(q), ff.ptr(kc[l, 0]), ff.ptr(kc[l, 1]), ff.ptr(o),
-                                                               B, 16, 8, ctx, ctx, ff.ptr(km), ctx,
+                                                               B, H, KV, ctx, ctx, ff.ptr(km), ctx,
                                                                1 / math.sqrt(128), ff.ptr(ws), nb, ff.stream_ptr()),
                          "attention_decode")
             med, _ = interleaved({"a": attn}, args.rounds, LAYERS, flush)
-            nbytes = 2 * B * 8 * ctx * 128 * 2
+            nbytes = 2 * B * KV * ctx * 128 * 2
             kern[f"attn_decode_ctx{ctx}"] = {"us": round(med["a"] * 1e3, 2), "kv_bytes": nbytes,
                                              "GBps": round(nbytes / med["a"] * 1e-6, 1)}
             del kc
         print(name, "kernels", json.dumps(kern), flush=True)
-        res["models"][name] = {"hidden": hidden, "intermediate": inter, "steps": rows, "kernels": kern,
+        res["models"][name] = {"rounds": args.rounds, "iters": args.iters, "hidden": hidden, "intermediate": inter,
+                               "layers": LAYERS, "heads": H, "kv_heads": KV,
+                               "steps": rows, "kernels": kern,
                                "hf_baseline": "timed" if hf is not None else why}
         lm.close()
         del hf, lm, rt
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if os.path.exists(args.out):                 # the models not run keep their recorded entries
+        old = json.load(open(args.out))
+        if not set(old.get("models", {})) <= set(res["models"]):     # a partial run: the file's header stays too
+            res = dict(old, models=dict(old["models"], **res["models"]))
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print("wrote", args.out)

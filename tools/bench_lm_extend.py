@@ -20,9 +20,18 @@ The attention kernel alone (acehip_attention_extend_bf16, B = 1, 16 / 8 heads) a
 (64, 1500), (512, 1500), (512, 8192): its plan, its time, and its floors — K and V read once per
 KV head plus q and o over HBM bandwidth (8 TB/s), and the causal 4·H·128·Σ(keys of query i) FLOP
 over the bf16 MFMA peak (2.5 PF).
-Writes profiles/lm_extend_bench.json.
 
-usage: bench_lm_extend.py [--out PATH] [--rounds N] [--iters N] [--models 0.6B,1.7B]
+With --models 4B the 4B's shape (36 layers, 2560 / 9728, 32 / 8 heads) runs the same arms, and —
+for every model whose heads / kv_heads is 4, whose prefill attention the handle sends to
+acehip_attention_extend_bf16 — a "prefill" entry: acehip_enc_prefill at B = 2, S = 1500 (row 1
+left-padded by 9), that attention launch alone (B = 2, n = S, pos = 0, cap = S, the mask) and the
+layer's four GEMMs alone at M = 3000 (QKV head-post, O residual, SwiGLU, down residual), with
+attention_share = layers · attention / prefill and attention_over_gemms.
+
+Writes profiles/lm_extend_bench.json; a run of some models replaces those models' entries of an
+existing file and keeps the others.
+
+usage: bench_lm_extend.py [--out PATH] [--rounds N] [--iters N] [--models 0.6B,1.7B,4B]
 """
 import argparse
 import json
@@ -39,9 +48,11 @@ from acehip.config import DiTConfig  # noqa: E402
 from acehip.lm import HipCausalLM, HipLMRuntime  # noqa: E402
 from acehip.weights import synth_text_encoder_weights  # noqa: E402
 
-VOCAB, LAYERS, S = 217204, 28, 1500
+VOCAB, S = 217204, 1500
 TARGETS = (64, 512)
-MODELS = {"0.6B": (1024, 3072), "1.7B": (2048, 6144)}
+# name -> (hidden, intermediate, layers, heads, kv_heads)
+MODELS = {"0.6B": (1024, 3072, 28, 16, 8), "1.7B": (2048, 6144, 28, 16, 8), "4B": (2560, 9728, 36, 32, 8)}
+PREFILL_B, PREFILL_PAD = 2, 9
 ATTN_SHAPES = ((64, 1500), (512, 1500), (512, 8192))
 H, KV = 16, 8
 HBM_BPS, MFMA_FLOPS = 8e12, 2.5e15
@@ -105,6 +116,57 @@ def bench_attention(dev, flush, rounds, gen):
     return out
 
 
+def bench_prefill(rt, cfg, dev, flush, rounds, iters, gen):
+    """acehip_enc_prefill at [PREFILL_B, S] on a heads / kv_heads = 4 runtime, its attention launch
+    and one layer's four GEMMs alone."""
+    Bp, hidden, inter = PREFILL_B, cfg.hidden_size, cfg.intermediate_size
+    Hq, Hkv, L = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.num_hidden_layers
+    M, qd, N3 = Bp * S, Hq * 128, (Hq + 2 * Hkv) * 128
+    scale = 1 / math.sqrt(128)
+    x = rt.embed(torch.randint(0, VOCAB, (Bp, S), device=dev, generator=gen))
+    km = torch.ones(Bp, S, dtype=torch.uint8, device=dev)
+    km[1, :PREFILL_PAD] = 0
+
+    def rnd(*shape, s=1.0):
+        return (torch.randn(*shape, device=dev, generator=gen) * s).bfloat16()
+    q, k, v = rnd(Bp, Hq, S, 128), rnd(Bp, Hkv, S, 128), rnd(Bp, Hkv, S, 128)
+    ao = torch.empty(M, qd, device=dev, dtype=torch.bfloat16)
+    nb = ff.lib().acehip_attention_extend_ws_bytes(Bp, Hq, S)
+    ws = torch.empty(nb, device=dev, dtype=torch.uint8)
+    xn, hb, res = rnd(M, hidden), rnd(M, inter), rnd(M, hidden)
+    wqkv, wo = rnd(N3, hidden, s=0.02), rnd(hidden, qd, s=0.02)
+    wgu, wdn = rnd(2 * inter, hidden, s=0.02), rnd(hidden, inter, s=0.02)
+    nw = torch.ones(128, device=dev, dtype=torch.bfloat16)
+    cs = torch.ones(S, 128, device=dev, dtype=torch.bfloat16)
+    hbo = torch.empty(M, inter, device=dev, dtype=torch.bfloat16)
+    lib, P, sp = ff.lib(), ff.ptr, ff.stream_ptr
+
+    def prefill():
+        rt.prefill(x, km)
+
+    def attn():
+        ff.check(lib.acehip_attention_extend_bf16(P(q), P(k), P(v), P(ao), Bp, Hq, Hkv, S, 0, S, P(km), S, scale, P(ws),
+                                                  nb, sp()), "attention_extend")
+
+    def gemms():
+        ff.check(lib.acehip_gemm_headpost_bf16(P(xn), hidden, P(wqkv), hidden, Bp, S, Hq, Hkv, Hkv, P(nw), P(nw), P(cs),
+                                               P(cs), 1e-6, P(q), P(k), P(v), sp()), "qkv")
+        ff.check(lib.acehip_gemm_bf16_ex(P(ao), qd, P(wo), qd, P(res), hidden, M, hidden, qd, None, 2, -1, sp()), "o")
+        ff.check(lib.acehip_gemm_bf16_ex(P(xn), hidden, P(wgu), hidden, P(hbo), inter, M, 2 * inter, hidden, None, 3, -1,
+                                         sp()), "swiglu")
+        ff.check(lib.acehip_gemm_bf16_ex(P(hb), inter, P(wdn), inter, P(res), hidden, M, hidden, inter, None, 2, -1,
+                                         sp()), "down")
+    med, spread = interleaved({"prefill_ms": (None, prefill), "attention_ms": (None, attn), "layer_gemms_ms": (None, gemms)},
+                              rounds, iters, flush)
+    plan = ff.attn_extend_plan(Bp, Hq, Hkv, S, 0)
+    row = dict(med, spread_ms=spread, B=Bp, S=S, left_pad_row1=PREFILL_PAD, layers=L,
+               attention_plan={f: plan[f] for f in ("units", "parts", "tiles", "tiles_per_part", "grid")})
+    row["attention_share_of_prefill"] = round(L * med["attention_ms"] / med["prefill_ms"], 3)
+    row["attention_over_layer_gemms"] = round(med["attention_ms"] / med["layer_gemms_ms"], 2)
+    row["prefill_tokens_per_s"] = round(M / med["prefill_ms"] * 1e3)
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "lm_extend_bench.json"))
@@ -117,18 +179,20 @@ def main():
     flush = torch.zeros(300 * (1 << 20) // 4, device=dev)
     g = torch.Generator(device=dev).manual_seed(0)
     res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "iters": args.iters, "vocab": VOCAB,
-           "layers": LAYERS, "S": S, "hbm_TBps_for_floor": HBM_BPS / 1e12, "mfma_PFLOPs_for_floor": MFMA_FLOPS / 1e15,
+           "S": S, "hbm_TBps_for_floor": HBM_BPS / 1e12, "mfma_PFLOPs_for_floor": MFMA_FLOPS / 1e15,
            "attention": bench_attention(dev, flush, args.rounds, g), "models": {}}
     prior = os.path.join(REPO, "profiles", "lm_score_bench.json")
     prior = json.load(open(prior))["models"] if os.path.exists(prior) else {}
     for name in args.models.split(","):
-        hidden, inter = MODELS[name]
+        hidden, inter, LAYERS, Hm, KVm = MODELS[name]
         cfg = DiTConfig(hidden_size=hidden, intermediate_size=inter, num_hidden_layers=LAYERS,
-                        num_attention_heads=H, num_key_value_heads=KV, head_dim=128, rms_norm_eps=1e-6,
+                        num_attention_heads=Hm, num_key_value_heads=KVm, head_dim=128, rms_norm_eps=1e-6,
                         rope_theta=1_000_000.0)
         W = synth_text_encoder_weights(cfg, VOCAB, seed=0, mode="bench", device=dev, dtype=torch.bfloat16,
                                        backend="torch")
-        rt = HipLMRuntime(cfg, 0, max_batch=2, capacity=S + 64, prefill_tokens=S + 64, score_slots=2)
+        wide = Hm == 4 * KVm
+        rt = HipLMRuntime(cfg, 0, max_batch=2, capacity=S + 64, prefill_tokens=(PREFILL_B if wide else 1) * (S + 64),
+                          score_slots=2)
         rt.load(W)
         del W
         lm = HipCausalLM(rt)
@@ -177,11 +241,20 @@ def main():
                 row["lm_score_bench_call_ms"] = was
             rows[f"T{T}"] = row
             print(name, f"T={T}", json.dumps(row), flush=True)
-        res["models"][name] = {"hidden": hidden, "intermediate": inter, "calls": rows}
+        res["models"][name] = {"rounds": args.rounds, "iters": args.iters, "hidden": hidden, "intermediate": inter,
+                               "layers": LAYERS, "heads": Hm, "kv_heads": KVm,
+                               "calls": rows}
+        if wide:
+            res["models"][name]["prefill"] = bench_prefill(rt, cfg, dev, flush, args.rounds, args.iters, g)
+            print(name, "prefill", json.dumps(res["models"][name]["prefill"]), flush=True)
         lm.close()
         del lm, rt
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if os.path.exists(args.out):                 # the models not run keep their recorded entries
+        old = json.load(open(args.out))
+        if not set(old.get("models", {})) <= set(res["models"]):     # a partial run: the file's header stays too
+            res = dict(old, models=dict(old["models"], **res["models"]))
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print("wrote", args.out)
