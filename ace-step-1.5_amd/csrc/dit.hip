@@ -21,7 +21,7 @@
 #include <vector>
 #include <cstring>
 
-#include "kernels.h"
+#include "layer_args.h"
 #include "../../include/acehip.h"
 
 using namespace acehip;
@@ -135,23 +135,9 @@ static int forward_f32(acehip_dit *h, const float *xt, const float *ctx, int Bx,
                        int t_stride, int Bc, int T, float *vt_out, hipStream_t s,
                        const acehip_attn_capture *cap = nullptr);
 
-// every GEMM of this runtime may use the handle's split-K workspace (small-M grids)
-static inline int hgemm(acehip_dit *h, GemmArgs g, hipStream_t s, RowAdd *defer = nullptr) {
-    g.ws = h->gemm_ws;
-    g.ws_bytes = h->gemm_ws ? GEMM_WS_BYTES : 0;
-    return gemm(g, s, defer);
-}
-
 namespace {
 
 thread_local std::string g_err;
-
-bf16_t *dalloc(acehip_dit *h, size_t elems) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(elems, 1) * 2) != hipSuccess) return nullptr;
-    h->allocs.push_back(p);
-    return (bf16_t *)p;
-}
 
 void add_slot(acehip_dit *h, const std::string &name, bf16_t *dst, std::vector<int64_t> shape,
               PackKind kind = P_COPY) {
@@ -170,27 +156,6 @@ int64_t numel(const std::vector<int64_t> &s) {
 
 // host-side bf16 rounding (same as device f2bf)
 inline bf16_t hf2bf(float f) { return f2bf(f); }
-
-int build_rope(acehip_dit *h) {
-    const int hd = h->cfg.head_dim, S = h->cfg.max_S;
-    std::vector<float> inv(hd / 2);
-    for (int i = 0; i < hd / 2; ++i) {
-        float v;
-        if (!h->inv_freq_override.empty()) v = h->inv_freq_override[i];
-        else v = 1.0f / powf(h->cfg.rope_theta, (float)(2 * i) / (float)hd);
-        inv[i] = bf2f(hf2bf(v));   // model.to(bf16) casts the inv_freq buffer (init_service_loader.py:81-89)
-    }
-    std::vector<bf16_t> c((size_t)S * hd), s((size_t)S * hd);
-    for (int p = 0; p < S; ++p)
-        for (int i = 0; i < hd; ++i) {
-            const float f = (float)p * inv[i % (hd / 2)];
-            c[(size_t)p * hd + i] = hf2bf((float)cos((double)f));
-            s[(size_t)p * hd + i] = hf2bf((float)sin((double)f));
-        }
-    HIP_TRY(hipMemcpy(h->rope_cos, c.data(), c.size() * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->rope_sin, s.data(), s.size() * 2, hipMemcpyHostToDevice));
-    return 0;
-}
 
 // record an event pair around `launch` when profiling is on
 template <class F>
@@ -261,7 +226,7 @@ int acehip_dit_create(int device, const acehip_dit_cfg *cfg, acehip_dit **out) {
     }
     const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, L = h->L;
     bool ok = true;
-    auto A = [&](size_t n) { bf16_t *p = dalloc(h, n); ok = ok && p; return p; };
+    auto A = [&](size_t n) { bf16_t *p = dev_alloc(h->allocs, n); ok = ok && p; return p; };
 
     h->tables = A((size_t)L * 6 * D);
     h->layers.resize(L);
@@ -478,9 +443,7 @@ int acehip_dit_set_weight(acehip_dit *h, const char *name, const void *ptr, int 
     }
     const hipMemcpyKind kind = (dtype == ACEHIP_F32 || on_device) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (s.kind == P_GU_GATE || s.kind == P_GU_UP) {
-        const int64_t F = sh[0], K = sh[1];
-        bf16_t *dst = s.dst + (s.kind == P_GU_UP ? 32 * K : 0);
-        HIP_TRY(hipMemcpy2D(dst, 64 * K * 2, src, 32 * K * 2, 32 * K * 2, F / 32, kind));
+        if (int rc = pack_gate_up(s.dst, src, sh[0], sh[1], s.kind == P_GU_UP, kind)) return rc;
         s.set = true;
         return 0;
     }
@@ -516,7 +479,9 @@ int acehip_dit_finalize(acehip_dit *h) {
         if (!kv.second.set) missing += kv.first + " ";
     if (!missing.empty()) return fail(ACEHIP_E_STATE, "dit_finalize: missing weights: " + missing.substr(0, 400));
     if (h->F % 32) return fail(ACEHIP_E_ARG, "intermediate must be a multiple of 32");
-    int rc = h->f32 ? build_rope_f32(h) : build_rope(h);
+    int rc = h->f32 ? build_rope_f32(h)
+                    : build_rope_tables(h->cfg.head_dim, h->cfg.max_S, h->cfg.rope_theta, h->inv_freq_override,
+                                        h->rope_cos, h->rope_sin);
     if (rc) return rc;
     if (!h->f32 && h->ts_cap < kTsCap && (rc = alloc_timesteps(h, kTsCap))) return rc;
     HIP_TRY(hipDeviceSynchronize());
@@ -533,10 +498,7 @@ int acehip_dit_set_condition(acehip_dit *h, const void *enc, int Bc, int Lenc, v
     hipStream_t s = (hipStream_t)stream;
     if (h->f32) return set_condition_f32(h, (const float *)enc, Bc, Lenc, s);
     const int D = h->D, kvd = h->kvd, M = Bc * Lenc;
-    GemmArgs g{};
-    g.A = (const bf16_t *)enc; g.lda = D; g.W = h->wce; g.ldw = D; g.C = h->E; g.ldc = D;
-    g.M = M; g.N = D; g.K = D; g.epi = EPI_STORE; g.bias = h->bce;
-    int rc = hgemm(h, g, s);
+    int rc = hgemm(h, lin_store((const bf16_t *)enc, D, h->wce, h->E, D, M, D, D, h->bce), s);
     if (rc) return rc;
     const size_t per = (size_t)Bc * kvd * Lenc;
     // the layers' K/V projections in GEMMs over groups of kv_group layers: M = Bc·Lenc rows ×
@@ -549,10 +511,8 @@ int acehip_dit_set_condition(acehip_dit *h, const void *enc, int Bc, int Lenc, v
         const int lg = l % G;
         if (lg == 0) {
             const int nl = std::min(G, h->L - l);
-            GemmArgs k{};
-            k.A = h->E; k.lda = D; k.W = h->wckv_all + (size_t)l * 2 * kvd * D; k.ldw = D; k.C = h->KVtmp;
-            k.ldc = ldkv; k.M = M; k.N = nl * 2 * kvd; k.K = D; k.epi = EPI_STORE;
-            if ((rc = hgemm(h, k, s))) return rc;
+            const bf16_t *wkv = h->wckv_all + (size_t)l * 2 * kvd * D;
+            if ((rc = hgemm(h, lin_store(h->E, D, wkv, h->KVtmp, ldkv, M, nl * 2 * kvd, D), s))) return rc;
         }
         HeadPostArgs p{};
         p.src = h->KVtmp + (size_t)lg * 2 * kvd; p.ld_src = ldkv; p.B = Bc; p.S = Lenc;
@@ -585,10 +545,8 @@ int acehip_dit_set_uniform_rows(acehip_dit *h, int first_row, void *stream) {
         int rc = gather_head_row(h->Vc + l * per + (size_t)first_row * kvd * Le, h->cfg.kv_heads, Le, h->cfg.heads,
                                  h->vnull, s);
         if (rc) return rc;
-        GemmArgs g{};
-        g.A = h->vnull; g.lda = qd; g.W = h->layers[l].wco; g.ldw = qd; g.C = h->cnull + (size_t)l * D; g.ldc = D;
-        g.M = 1; g.N = D; g.K = qd; g.epi = EPI_STORE;
-        if ((rc = hgemm(h, g, s))) return rc;
+        if ((rc = hgemm(h, lin_store(h->vnull, qd, h->layers[l].wco, h->cnull + (size_t)l * D, D, 1, D, qd), s)))
+            return rc;
     }
     h->uniform_from = first_row;
     return 0;
@@ -749,11 +707,8 @@ static int forward_bf16(acehip_dit *h, const void *xt, const void *ctx, int Bx, 
         HIP_TRY(hipGraphLaunch(h->gexec, s));
     }
     // proj_out (base:1491-1501) on the normed output XN
-    GemmArgs po{};
-    po.A = h->XN; po.lda = h->D; po.W = h->wout; po.ldw = h->D;
-    po.C = (T % 2 == 0) ? (bf16_t *)vt_out : h->O2; po.ldc = 128;
-    po.M = M; po.N = 128; po.K = h->D; po.epi = EPI_STORE; po.bias = h->bout;
-    RUN(hgemm(h, po, s));
+    bf16_t *po = (T % 2 == 0) ? (bf16_t *)vt_out : h->O2;
+    RUN(hgemm(h, lin_store(h->XN, h->D, h->wout, po, 128, M, 128, h->D, h->bout), s));
     if (T % 2) RUN(crop_rows(h->O2, Bc, 2 * S, T, 64, (bf16_t *)vt_out, s));
 #undef RUN
     return 0;
@@ -819,10 +774,7 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
     RUN(modulation(h->sst_out, 1, 2, h->temb, Bc, D, h->mod_out, s));
 
     // proj_in (base:1347-1358) over the packed patches Xin
-    GemmArgs g{};
-    g.A = h->Xin; g.lda = 384; g.W = h->win; g.ldw = 384; g.C = h->X; g.ldc = D;
-    g.M = dup ? S : M; g.N = D; g.K = 384; g.epi = EPI_STORE; g.bias = h->bin;
-    RUN(hgemm(h, g, s));
+    RUN(hgemm(h, lin_store(h->Xin, 384, h->win, h->X, D, dup ? S : M, D, 384, h->bin), s));
 
     const bool fuse_rowadd = knobs().fuse_rowadd != 0;
     const size_t cper = (size_t)Bc * kvd * Le;
@@ -841,21 +793,14 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
         RUN(rmsnorm_mod(h->X, ly.n_sa, md + 0 * D, md + 1 * D, mbs, S, h->XN, Ms, D, eps, s, pend));
         pend = RowAdd{};
         // QKV projection with q/k RMSNorm + RoPE + head-major scatter fused in the epilogue
-        GemmArgs q{};
-        q.A = h->XN; q.lda = D; q.W = ly.wqkv; q.ldw = D;
-        q.M = Ms; q.N = qd + 2 * kvd; q.K = D; q.epi = EPI_HEADPOST;
-        q.hp.B = Bs; q.hp.S = S; q.hp.nq = H; q.hp.nk = KV; q.hp.nv = KV; q.hp.qw = ly.qn; q.hp.kw = ly.kn;
-        q.hp.cos = h->rope_cos; q.hp.sin = h->rope_sin;
-        q.hp.q = h->Qh; q.hp.k = h->Kh; q.hp.v = h->Vh; q.hp.S_dst = S; q.hp.eps = eps;
+        const GemmArgs q = lin_headpost(h->XN, D, ly.wqkv, D, Bs, S, H, KV, KV, ly.qn, ly.kn, h->rope_cos, h->rope_sin,
+                                        eps, HeadDst{h->Qh, h->Kh, h->Vh, S, 0});
         RUN(timed(h, 2, s, [&] { return hgemm(h, q, s); }));
         RUN(timed(h, h->sliding[l] ? 5 : 4, s, [&] {
             return attention(h->Qh, h->Kh, h->Vh, h->AO, Bs, H, KV, S, S, h->sliding[l] ? h->cfg.window : -1,
                              scale, qd, h->attn_ws, s);
         }));
-        GemmArgs o{};
-        o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
-        o.M = Ms; o.N = D; o.K = qd; o.epi = EPI_GATED_RES; o.res = h->X; o.ldr = D;
-        o.gate = md + 2 * D; o.gate_bstride = mbs; o.rows_per_batch = S;
+        const GemmArgs o = lin_gated_res(h->AO, qd, ly.wo, h->X, D, Ms, D, qd, md + 2 * D, mbs, S);
         const bool defer_o = fuse_rowadd && Bs == Bc && (Mq == M || Mq == 0);
         RUN(timed(h, 3, s, [&] { return hgemm(h, o, s, defer_o ? &pend : nullptr); }));
         for (int b = Bs; b < Bc; ++b)
@@ -865,11 +810,8 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
         if (Mq > 0) {
             RUN(rmsnorm_mod(h->X, ly.n_ca, nullptr, nullptr, 0, S, h->XN, Mq, D, eps, s, pend));
             pend = RowAdd{};
-            GemmArgs cq{};
-            cq.A = h->XN; cq.lda = D; cq.W = ly.wcq; cq.ldw = D;
-            cq.M = Mq; cq.N = qd; cq.K = D; cq.epi = EPI_HEADPOST;
-            cq.hp.B = Bq; cq.hp.S = S; cq.hp.nq = H; cq.hp.qw = ly.cqn; cq.hp.q = h->Qh; cq.hp.S_dst = S;
-            cq.hp.eps = eps;
+            GemmArgs cq = lin_headpost(h->XN, D, ly.wcq, D, Bq, S, H, 0, 0, ly.cqn, nullptr, nullptr, nullptr, eps,
+                                       HeadDst{h->Qh, nullptr, nullptr, S, 0});   // q heads only, no RoPE
             cq.ws = h->gemm_ws;
             cq.ws_bytes = h->gemm_ws ? GEMM_WS_BYTES : 0;
             AttnProbsSel sel;
@@ -897,9 +839,7 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
                                      h->attn_ws, s);
                 }));
             }
-            GemmArgs co{};
-            co.A = h->AO; co.lda = qd; co.W = ly.wco; co.ldw = qd; co.C = h->X; co.ldc = D;
-            co.M = Mq; co.N = D; co.K = qd; co.epi = EPI_RES; co.res = h->X; co.ldr = D;
+            const GemmArgs co = lin_res(h->AO, qd, ly.wco, h->X, D, Mq, D, qd);
             RUN(timed(h, 3, s, [&] { return hgemm(h, co, s, fuse_rowadd ? &pend : nullptr); }));
         }
         // --- SwiGLU MLP with AdaLN-Zero (base:528-533); the null rows' constant cross-O output
@@ -916,14 +856,9 @@ static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, 
             }
         }
         RUN(rmsnorm_mod(h->X, ly.n_mlp, md + 3 * D, md + 4 * D, mbs, S, h->XN, M, D, eps, s, ra));
-        GemmArgs gu{};
-        gu.A = h->XN; gu.lda = D; gu.W = ly.wgu; gu.ldw = D; gu.C = h->Hb; gu.ldc = F;
-        gu.M = M; gu.N = 2 * F; gu.K = D; gu.epi = EPI_SWIGLU;
+        const GemmArgs gu = lin_swiglu(h->XN, D, ly.wgu, h->Hb, F, M, D);
         RUN(timed(h, 0, s, [&] { return hgemm(h, gu, s); }));
-        GemmArgs dn{};
-        dn.A = h->Hb; dn.lda = F; dn.W = ly.wdown; dn.ldw = F; dn.C = h->X; dn.ldc = D;
-        dn.M = M; dn.N = D; dn.K = F; dn.epi = EPI_GATED_RES; dn.res = h->X; dn.ldr = D;
-        dn.gate = md + 5 * D; dn.gate_bstride = mbs; dn.rows_per_batch = S;
+        const GemmArgs dn = lin_gated_res(h->Hb, F, ly.wdown, h->X, D, M, D, F, md + 5 * D, mbs, S);
         RUN(timed(h, 1, s, [&] { return hgemm(h, dn, s, fuse_rowadd ? &pend : nullptr); }));
     }
     // norm_out AdaLN (base:1491-1497); proj_out runs after the body
@@ -1127,14 +1062,10 @@ int acehip_gemm_headpost_bf16(const void *A, int lda, const void *W, int K, int 
                               float eps, void *q, void *k, void *v, void *stream) {
     if (!A || !W) return fail(ACEHIP_E_ARG, "null argument");
     if ((nq && !q) || (nk && !k) || (nv && !v)) return fail(ACEHIP_E_ARG, "missing head output");
-    GemmArgs g{};
-    g.A = (const bf16_t *)A; g.lda = lda; g.W = (const bf16_t *)W; g.ldw = K;
-    g.M = B * S; g.N = (nq + nk + nv) * 128; g.K = K; g.epi = EPI_HEADPOST;
-    if (g.M <= 0 || K % 64 || K <= 0) return fail(ACEHIP_E_ARG, "gemm_headpost: shape");
-    g.hp.B = B; g.hp.S = S; g.hp.nq = nq; g.hp.nk = nk; g.hp.nv = nv;
-    g.hp.qw = (const bf16_t *)qw; g.hp.kw = (const bf16_t *)kw;
-    g.hp.cos = (const bf16_t *)cos; g.hp.sin = (const bf16_t *)sin;
-    g.hp.q = (bf16_t *)q; g.hp.k = (bf16_t *)k; g.hp.v = (bf16_t *)v; g.hp.S_dst = S; g.hp.eps = eps;
+    if (B * S <= 0 || K % 64 || K <= 0) return fail(ACEHIP_E_ARG, "gemm_headpost: shape");
+    GemmArgs g = lin_headpost((const bf16_t *)A, lda, (const bf16_t *)W, K, B, S, nq, nk, nv, (const bf16_t *)qw,
+                              (const bf16_t *)kw, (const bf16_t *)cos, (const bf16_t *)sin, eps,
+                              HeadDst{(bf16_t *)q, (bf16_t *)k, (bf16_t *)v, S, 0});
     g.ws = abi_gemm_ws();
     g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
     return gemm(g, (hipStream_t)stream);
@@ -1168,10 +1099,8 @@ int acehip_cross_attn_bf16(const void *xn, const void *wq, const void *qnw, cons
     if (force < -1 || force > 1) return fail(ACEHIP_E_ARG, "cross_attn: force must be -1, 0 or 1");
     *path = -1;
     hipStream_t s = (hipStream_t)stream;
-    GemmArgs cq{};
-    cq.A = (const bf16_t *)xn; cq.lda = D; cq.W = (const bf16_t *)wq; cq.ldw = D;
-    cq.M = B * S; cq.N = H * 128; cq.K = D; cq.epi = EPI_HEADPOST;
-    cq.hp.B = B; cq.hp.S = S; cq.hp.nq = H; cq.hp.qw = (const bf16_t *)qnw; cq.hp.S_dst = S; cq.hp.eps = eps;
+    GemmArgs cq = lin_headpost((const bf16_t *)xn, D, (const bf16_t *)wq, D, B, S, H, 0, 0, (const bf16_t *)qnw, nullptr,
+                               nullptr, nullptr, eps, HeadDst{nullptr, nullptr, nullptr, S, 0});
     cq.ws = abi_gemm_ws();
     cq.ws_bytes = cq.ws ? GEMM_WS_BYTES : 0;
     const int64_t qd = (int64_t)H * 128;

@@ -20,15 +20,28 @@
 //
 // Runs once per song (twice in the reference, service_generate_execute.py:123
 // and base:1820), so it is launch-count-light rather than tuned: every GEMM
-// is the DiT's MFMA GEMM, every attention the DiT's flash kernel.  The one exception is a causal
-// stack with heads / kv_heads = 4 (the 4B language model): the flash kernels take ratios 1 and 2,
-// so its forward / prefill attention is attention_extend at pos = 0 over the head-post buffers
-// (enc_forward_impl), which writes a query row without any admissible key as zeros.
+// is the DiT's MFMA GEMM, every attention the DiT's flash kernel.
+//
+// One layer loop (enc_run) serves the four entries that run the stack; each describes its pass
+// in an EncPass: rows per sequence, first RoPE row, where head-post writes k / v, which attention
+// runs and what follows the final norm.
+//
+//   entry     rows   k / v go to                  attention                   out
+//   forward   S      Kh / Vh                      flash, or extend (below)    every row (or proj_out)
+//   prefill   S      Kh / Vh, copied to cache     as forward                  last row of each sequence
+//   decode    1      cache slot pos               attention_decode            every row
+//   extend    n      cache slots pos .. pos+n−1   attention_extend            every row
+//                    of rows row0 .. row0+B−1
+//
+// A causal stack with heads / kv_heads = 4 (the 4B language model) has no flash kernel (those
+// take ratios 1 and 2): its forward / prefill attention is attention_extend at pos = 0 over the
+// head-post buffers, the S positions as S new queries over a "cache" of S rows, which writes a
+// query row without any admissible key as zeros.
 #include <cmath>
 #include <map>
 #include <vector>
 
-#include "kernels.h"
+#include "layer_args.h"
 #include "../../include/acehip.h"
 
 using namespace acehip;
@@ -40,10 +53,11 @@ struct acehip_enc {
     int D = 0, F = 0, qd = 0, kvd = 0, L = 0;
     bool finalized = false;
     std::vector<void *> allocs;
+    enum Pack { P_COPY, P_GU_GATE, P_GU_UP };   // gate / up: interleaved panels (pack_gate_up)
     struct Slot {
         bf16_t *dst;
         std::vector<int64_t> shape;
-        int kind;   // 0 copy, 1 gate (interleave), 2 up (interleave), 3 proj_out rows padded to 128
+        Pack kind;
         bool set;
     };
     std::map<std::string, Slot> slots;
@@ -67,44 +81,6 @@ struct acehip_enc {
     void *ext_ws = nullptr;
     size_t ext_ws_bytes = 0;
 };
-
-// every GEMM of this runtime may use the handle's split-K workspace (small-M grids)
-static inline int hgemm(acehip_enc *h, GemmArgs g, hipStream_t s, RowAdd *defer = nullptr) {
-    g.ws = h->gemm_ws;
-    g.ws_bytes = h->gemm_ws ? GEMM_WS_BYTES : 0;
-    return gemm(g, s, defer);
-}
-
-namespace {
-
-bf16_t *enc_alloc(acehip_enc *h, size_t elems) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(elems, 1) * 2) != hipSuccess) return nullptr;
-    h->allocs.push_back(p);
-    return (bf16_t *)p;
-}
-
-int enc_build_rope(acehip_enc *h) {
-    const int hd = h->cfg.head_dim, S = h->cfg.max_S;
-    std::vector<float> inv(hd / 2);
-    for (int i = 0; i < hd / 2; ++i) {
-        const float v = h->inv_freq_override.empty() ? 1.0f / powf(h->cfg.rope_theta, (float)(2 * i) / (float)hd)
-                                                     : h->inv_freq_override[i];
-        inv[i] = bf2f(f2bf(v));   // model.to(bf16) casts the rotary inv_freq buffer too (see dit.hip)
-    }
-    std::vector<bf16_t> c((size_t)S * hd), s((size_t)S * hd);
-    for (int p = 0; p < S; ++p)
-        for (int i = 0; i < hd; ++i) {
-            const float f = (float)p * inv[i % (hd / 2)];
-            c[(size_t)p * hd + i] = f2bf((float)cos((double)f));
-            s[(size_t)p * hd + i] = f2bf((float)sin((double)f));
-        }
-    HIP_TRY(hipMemcpy(h->rope_cos, c.data(), c.size() * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->rope_sin, s.data(), s.size() * 2, hipMemcpyHostToDevice));
-    return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -146,8 +122,9 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
     h->cfg.sliding = nullptr;
     const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd;
     bool ok = true;
-    auto A = [&](size_t n) { bf16_t *p = enc_alloc(h, n); ok = ok && p; return p; };
-    auto slot = [&](const std::string &n, bf16_t *dst, std::vector<int64_t> shape, int kind = 0) {
+    auto A = [&](size_t n) { bf16_t *p = dev_alloc(h->allocs, n); ok = ok && p; return p; };
+    auto slot = [&](const std::string &n, bf16_t *dst, std::vector<int64_t> shape,
+                    acehip_enc::Pack kind = acehip_enc::P_COPY) {
         h->slots[n] = acehip_enc::Slot{dst, std::move(shape), kind, false};
     };
     h->layers.resize(h->L);
@@ -166,8 +143,8 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
         slot(p + ".self_attn.o_proj.weight", ly.wo, {D, qd});
         slot(p + ".self_attn.q_norm.weight", ly.qn, {128});
         slot(p + ".self_attn.k_norm.weight", ly.kn, {128});
-        slot(p + ".mlp.gate_proj.weight", ly.wgu, {F, D}, 1);
-        slot(p + ".mlp.up_proj.weight", ly.wgu, {F, D}, 2);
+        slot(p + ".mlp.gate_proj.weight", ly.wgu, {F, D}, acehip_enc::P_GU_GATE);
+        slot(p + ".mlp.up_proj.weight", ly.wgu, {F, D}, acehip_enc::P_GU_UP);
         slot(p + ".mlp.down_proj.weight", ly.wdown, {D, F});
     }
     if (ok && cfg->in_dim) {
@@ -199,12 +176,12 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
     h->rope_cos = A((size_t)cfg->max_S * 128); h->rope_sin = A((size_t)cfg->max_S * 128);
     if (ok) {
         const size_t wb = attention_ws_bytes();
-        h->attn_ws = enc_alloc(h, (wb + 1) / 2);
+        h->attn_ws = dev_alloc(h->allocs, (wb + 1) / 2);
         ok = h->attn_ws && hipMemset(h->attn_ws, 0, wb) == hipSuccess;
     }
     if (ok && wide) {   // the forward's attention is attention_extend: its partials, cache or not
         h->ext_ws_bytes = attention_extend_ws_bytes(cfg->max_tokens, cfg->heads, cfg->max_tokens);
-        h->ext_ws = enc_alloc(h, h->ext_ws_bytes / 2);
+        h->ext_ws = dev_alloc(h->allocs, h->ext_ws_bytes / 2);
         ok = h->ext_ws != nullptr;
     }
     if (!ok) {
@@ -246,10 +223,10 @@ int acehip_enc_set_weight(acehip_enc *h, const char *name, const void *ptr, int 
     } else {
         HIP_TRY(hipMemcpy(hb.data(), ptr, n * 2, k));
     }
-    if (s.kind == 1 || s.kind == 2) {   // gate/up interleaved in 32-row panels (SwiGLU epilogue layout)
-        const int64_t F = s.shape[0], K = s.shape[1];
-        bf16_t *dst = s.dst + (s.kind == 2 ? 32 * K : 0);
-        HIP_TRY(hipMemcpy2D(dst, 64 * K * 2, hb.data(), 32 * K * 2, 32 * K * 2, F / 32, hipMemcpyHostToDevice));
+    if (s.kind != acehip_enc::P_COPY) {
+        const int rc = pack_gate_up(s.dst, hb.data(), s.shape[0], s.shape[1], s.kind == acehip_enc::P_GU_UP,
+                                    hipMemcpyHostToDevice);
+        if (rc) return rc;
     } else {
         HIP_TRY(hipMemcpy(s.dst, hb.data(), n * 2, hipMemcpyHostToDevice));
     }
@@ -265,7 +242,8 @@ int acehip_enc_finalize(acehip_enc *h) {
         if (!kv.second.set) missing += kv.first + " ";
     if (!missing.empty()) return fail(ACEHIP_E_STATE, "enc_finalize: missing weights: " + missing.substr(0, 400));
     if (h->F % 32) return fail(ACEHIP_E_ARG, "intermediate must be a multiple of 32");
-    const int rc = enc_build_rope(h);
+    const int rc = build_rope_tables(h->cfg.head_dim, h->cfg.max_S, h->cfg.rope_theta, h->inv_freq_override,
+                                     h->rope_cos, h->rope_sin);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     h->finalized = true;
@@ -277,87 +255,101 @@ int acehip_enc_embed(acehip_enc *h, const void *x, int M, void *out, void *strea
     if (!h->finalized || !h->wemb) return fail(ACEHIP_E_STATE, "enc_embed: not finalized / no embed_tokens");
     if (M <= 0) return M == 0 ? 0 : fail(ACEHIP_E_ARG, "enc_embed: M");
     HIP_TRY(hipSetDevice(h->device));
-    GemmArgs g{};
-    g.A = (const bf16_t *)x; g.lda = h->cfg.in_dim; g.W = h->wemb; g.ldw = h->cfg.in_dim;
-    g.C = (bf16_t *)out; g.ldc = h->D; g.M = M; g.N = h->D; g.K = h->cfg.in_dim;
-    g.epi = EPI_STORE; g.bias = h->bemb;
-    return gemm(g, (hipStream_t)stream);
+    const int K = h->cfg.in_dim;
+    return gemm(lin_store((const bf16_t *)x, K, h->wemb, (bf16_t *)out, h->D, M, h->D, K, h->bemb), (hipStream_t)stream);
 }
 
 }  // extern "C"
 
-// acehip_enc_forward's body.  prefill: every layer's K (normed, rotated) and V also land in
-// cache rows [0, S), and out receives only the final-norm row of each sequence's last position.
-static int enc_forward_impl(acehip_enc *h, const void *x, const uint8_t *kmask, int B, int S, void *out, void *stream,
-                            bool prefill) {
-    hipStream_t s = (hipStream_t)stream;
-    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, M = B * S;
+// One pass of the layer stack over M = B·n rows of x: what an entry hands to enc_run.
+struct EncPass {
+    int B, n;             // sequences, rows per sequence (S for forward / prefill, 1 for decode)
+    int pos;              // first RoPE row, and with KV_CACHE the first cache position written
+    int row0;             // first cache row (extend); 0 otherwise
+    enum { KV_BUFFERS, KV_CACHE } kv;   // head-post writes k / v to Kh / Vh [B][KV][n][128], or into the
+                                        // cache at `pos` (q compact [B][H][n][128]); the attention reads the same
+    bool copy_to_cache;   // prefill: Kh / Vh → cache rows [0, n) after head-post
+    enum { ATT_FLASH, ATT_EXTEND, ATT_DECODE } att;
+    const uint8_t *kmask; // key-padding mask [B][mask_ld], or null
+    int mask_ld;
+    enum { OUT_ALL_ROWS, OUT_LAST_ROW, OUT_PROJ } tail;   // after the final norm: every row, each sequence's
+                                                          // last row, or the detokenizer's proj_out
+};
+
+// forward / prefill: the flash kernels take heads / kv_heads 1 and 2; at 4 (causal by enc_create) the
+// S positions are S new queries over a "cache" of S rows, the head-post buffers
+static EncPass enc_buffer_pass(const acehip_enc *h, const uint8_t *kmask, int B, int S, bool prefill) {
+    EncPass p{};
+    p.B = B; p.n = S;
+    p.kv = EncPass::KV_BUFFERS; p.copy_to_cache = prefill;
+    p.att = h->cfg.heads / h->cfg.kv_heads == 4 ? EncPass::ATT_EXTEND : EncPass::ATT_FLASH;
+    p.kmask = kmask; p.mask_ld = S;
+    p.tail = prefill ? EncPass::OUT_LAST_ROW : h->cfg.out_dim ? EncPass::OUT_PROJ : EncPass::OUT_ALL_ROWS;
+    return p;
+}
+
+static int enc_run(acehip_enc *h, const void *x, const EncPass &p, void *out, hipStream_t s) {
+    const int D = h->D, F = h->F, qd = h->qd, cap = h->kv_cap, B = p.B, n = p.n, M = B * n;
     const int H = h->cfg.heads, KV = h->cfg.kv_heads;
     const float eps = h->cfg.eps, scale = 1.0f / sqrtf(128.0f);
+    const bool cache = p.kv == EncPass::KV_CACHE;
+    // cache layer l: [kv_B][KV][cap][128]; the pass's rows start row_off in
+    const size_t per = (size_t)h->kv_B * KV * cap * 128, row_off = (size_t)p.row0 * KV * cap * 128;
+    const int kv_rows = cache ? cap : n;   // rows per KV head where k / v land
+    const bf16_t *rcos = h->rope_cos + (size_t)p.pos * 128, *rsin = h->rope_sin + (size_t)p.pos * 128;
     int rc;
 #define RUN(e) do { if ((rc = (e))) return rc; } while (0)
     HIP_TRY(hipMemcpyAsync(h->X, x, (size_t)M * D * 2, hipMemcpyDeviceToDevice, s));
-    // few tokens (text / lyric encoders): the O and down GEMMs take gemm's split-K path and
-    // leave their residual epilogue to the next norm (`pend`, as in the DiT forward)
+    // few rows (text / lyric encoders, the token loop): the O and down GEMMs take gemm's split-K
+    // path and leave their residual epilogue to the next norm (`pend`, as in the DiT forward)
     RowAdd pend{};
     for (int l = 0; l < h->L; ++l) {
         const auto &ly = h->layers[l];
-        RUN(rmsnorm_mod(h->X, ly.ln1, nullptr, nullptr, 0, S, h->XN, M, D, eps, s, pend));
+        bf16_t *Kl = cache ? h->Kc + l * per + row_off : h->Kh, *Vl = cache ? h->Vc + l * per + row_off : h->Vh;
+        RUN(rmsnorm_mod(h->X, ly.ln1, nullptr, nullptr, 0, n, h->XN, M, D, eps, s, pend));
         pend = RowAdd{};
-        GemmArgs q{};
-        q.A = h->XN; q.lda = D; q.W = ly.wqkv; q.ldw = D;
-        q.M = M; q.N = qd + 2 * kvd; q.K = D; q.epi = EPI_HEADPOST;
-        q.hp.B = B; q.hp.S = S; q.hp.nq = H; q.hp.nk = KV; q.hp.nv = KV; q.hp.qw = ly.qn; q.hp.kw = ly.kn;
-        q.hp.cos = h->rope_cos; q.hp.sin = h->rope_sin;
-        q.hp.q = h->Qh; q.hp.k = h->Kh; q.hp.v = h->Vh; q.hp.S_dst = S; q.hp.eps = eps;
-        RUN(hgemm(h, q, s));
-        if (prefill) {   // [B·KV] blocks of S rows → the same blocks of the cache, kv_cap rows apart
-            const size_t per = (size_t)h->kv_B * KV * h->kv_cap * 128;
-            HIP_TRY(hipMemcpy2DAsync(h->Kc + l * per, (size_t)h->kv_cap * 256, h->Kh, (size_t)S * 256, (size_t)S * 256,
+        const HeadDst dst = cache ? HeadDst{h->Qh, Kl + (size_t)p.pos * 128, Vl + (size_t)p.pos * 128, cap, n}
+                                  : HeadDst{h->Qh, Kl, Vl, n, 0};
+        RUN(hgemm(h, lin_headpost(h->XN, D, ly.wqkv, D, B, n, H, KV, KV, ly.qn, ly.kn, rcos, rsin, eps, dst), s));
+        if (p.copy_to_cache) {   // [B·KV] blocks of n rows → the same blocks of the cache, cap rows apart
+            HIP_TRY(hipMemcpy2DAsync(h->Kc + l * per, (size_t)cap * 256, h->Kh, (size_t)n * 256, (size_t)n * 256,
                                      (size_t)B * KV, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(hipMemcpy2DAsync(h->Vc + l * per, (size_t)h->kv_cap * 256, h->Vh, (size_t)S * 256, (size_t)S * 256,
+            HIP_TRY(hipMemcpy2DAsync(h->Vc + l * per, (size_t)cap * 256, h->Vh, (size_t)n * 256, (size_t)n * 256,
                                      (size_t)B * KV, hipMemcpyDeviceToDevice, s));
         }
-        // layer kind: 0 full, 1 band |i−j| <= window, 2 causal (the Qwen3 text encoder)
-        const int win = h->sliding[l] == 2 ? ATTN_CAUSAL : h->sliding[l] ? h->cfg.window : -1;
-        if (H / KV == 4)   // causal by enc_create; the flash kernels take ratios 1 and 2 only: the S
-                           // positions as S new queries over a "cache" of S rows, the head-post buffers
-            RUN(attention_extend(h->Qh, h->Kh, h->Vh, h->AO, B, H, KV, S, 0, S, kmask, S, scale, h->ext_ws,
-                                 h->ext_ws_bytes, s));
-        else
-            RUN(attention(h->Qh, h->Kh, h->Vh, h->AO, B, H, KV, S, S, win, scale, qd, h->attn_ws, s, kmask));
-        GemmArgs o{};
-        o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
-        o.M = M; o.N = D; o.K = qd; o.epi = EPI_RES; o.res = h->X; o.ldr = D;
-        RUN(hgemm(h, o, s, &pend));
-        RUN(rmsnorm_mod(h->X, ly.ln2, nullptr, nullptr, 0, S, h->XN, M, D, eps, s, pend));
+        switch (p.att) {
+        case EncPass::ATT_FLASH: {
+            // layer kind: 0 full, 1 band |i−j| <= window, 2 causal (the Qwen3 text encoder)
+            const int win = h->sliding[l] == 2 ? ATTN_CAUSAL : h->sliding[l] ? h->cfg.window : -1;
+            RUN(attention(h->Qh, Kl, Vl, h->AO, B, H, KV, n, n, win, scale, qd, h->attn_ws, s, p.kmask));
+            break;
+        }
+        case EncPass::ATT_EXTEND:
+            RUN(attention_extend(h->Qh, Kl, Vl, h->AO, B, H, KV, n, p.pos, kv_rows, p.kmask, p.mask_ld, scale,
+                                 h->ext_ws, h->ext_ws_bytes, s));
+            break;
+        case EncPass::ATT_DECODE:
+            RUN(attention_decode(h->Qh, Kl, Vl, h->AO, B, H, KV, p.pos + 1, kv_rows, p.kmask, p.mask_ld, scale,
+                                 h->dec_ws, h->dec_ws_bytes, s));
+            break;
+        }
+        RUN(hgemm(h, lin_res(h->AO, qd, ly.wo, h->X, D, M, D, qd), s, &pend));
+        RUN(rmsnorm_mod(h->X, ly.ln2, nullptr, nullptr, 0, n, h->XN, M, D, eps, s, pend));
         pend = RowAdd{};
-        GemmArgs gu{};
-        gu.A = h->XN; gu.lda = D; gu.W = ly.wgu; gu.ldw = D; gu.C = h->Hb; gu.ldc = F;
-        gu.M = M; gu.N = 2 * F; gu.K = D; gu.epi = EPI_SWIGLU;
-        RUN(hgemm(h, gu, s));
-        GemmArgs dn{};
-        dn.A = h->Hb; dn.lda = F; dn.W = ly.wdown; dn.ldw = F; dn.C = h->X; dn.ldc = D;
-        dn.M = M; dn.N = D; dn.K = F; dn.epi = EPI_RES; dn.res = h->X; dn.ldr = D;
-        RUN(hgemm(h, dn, s, &pend));
+        RUN(hgemm(h, lin_swiglu(h->XN, D, ly.wgu, h->Hb, F, M, D), s));
+        RUN(hgemm(h, lin_res(h->Hb, F, ly.wdown, h->X, D, M, D, F), s, &pend));
     }
-    if (prefill) {
-        RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, S, h->XN, M, D, eps, s, pend));
-        HIP_TRY(hipMemcpy2DAsync(out, (size_t)D * 2, h->XN + (size_t)(S - 1) * D, (size_t)S * D * 2, (size_t)D * 2, B,
+    bf16_t *normed = p.tail == EncPass::OUT_ALL_ROWS ? (bf16_t *)out : h->XN;
+    RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, n, normed, M, D, eps, s, pend));
+    if (p.tail == EncPass::OUT_LAST_ROW) {
+        HIP_TRY(hipMemcpy2DAsync(out, (size_t)D * 2, h->XN + (size_t)(n - 1) * D, (size_t)n * D * 2, (size_t)D * 2, B,
                                  hipMemcpyDeviceToDevice, s));
-        return 0;
     }
-    if (!h->cfg.out_dim) {
-        RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, S, (bf16_t *)out, M, D, eps, s, pend));
-        return 0;
+    if (p.tail == EncPass::OUT_PROJ) {
+        // detokenizer proj_out (base:991): rows padded to 128 with zeros, then the used columns
+        RUN(hgemm(h, lin_store(h->XN, D, h->wout, h->O128, 128, M, 128, D, h->bout), s));
+        RUN(copy_cols(h->O128, 128, (bf16_t *)out, h->cfg.out_dim, M, h->cfg.out_dim, s));
     }
-    // detokenizer proj_out (base:991): rows padded to 128 with zeros, then the used columns
-    RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, S, h->XN, M, D, eps, s, pend));
-    GemmArgs po{};
-    po.A = h->XN; po.lda = D; po.W = h->wout; po.ldw = D; po.C = h->O128; po.ldc = 128;
-    po.M = M; po.N = 128; po.K = D; po.epi = EPI_STORE; po.bias = h->bout;
-    RUN(hgemm(h, po, s));
-    RUN(copy_cols(h->O128, 128, (bf16_t *)out, h->cfg.out_dim, M, h->cfg.out_dim, s));
 #undef RUN
     return 0;
 }
@@ -370,7 +362,7 @@ int acehip_enc_forward(acehip_enc *h, const void *x, const uint8_t *kmask, int B
     if (B <= 0 || S <= 0 || S > h->cfg.max_S || (int64_t)B * S > h->cfg.max_tokens)
         return fail(ACEHIP_E_ARG, "enc_forward: B*S / S out of range");
     HIP_TRY(hipSetDevice(h->device));
-    return enc_forward_impl(h, x, kmask, B, S, out, stream, false);
+    return enc_run(h, x, enc_buffer_pass(h, kmask, B, S, false), out, (hipStream_t)stream);
 }
 
 // ---- token loop: K/V cache, prefill, one-token decode (acestep/llm_inference.py:416-438) ----
@@ -399,14 +391,14 @@ int acehip_enc_kv_create(acehip_enc *h, int max_B, int capacity) {
     h->kv_tried = true;
     const size_t per = (size_t)max_B * h->cfg.kv_heads * capacity * 128;
     h->dec_ws_bytes = attention_decode_ws_bytes(max_B, h->cfg.heads);
-    bf16_t *kc = enc_alloc(h, per * h->L), *vc = kc ? enc_alloc(h, per * h->L) : nullptr;
-    void *ws = vc ? enc_alloc(h, h->dec_ws_bytes / 2) : nullptr;
+    bf16_t *kc = dev_alloc(h->allocs, per * h->L), *vc = kc ? dev_alloc(h->allocs, per * h->L) : nullptr;
+    void *ws = vc ? dev_alloc(h->allocs, h->dec_ws_bytes / 2) : nullptr;
     // a heads/kv_heads = 4 handle has had its extend workspace since enc_create, sized for
     // max_tokens sequences: no smaller than this bound (max_B <= max_tokens)
     void *xws = h->ext_ws;
     if (!xws) {
         h->ext_ws_bytes = attention_extend_ws_bytes(max_B, h->cfg.heads, h->cfg.max_tokens);
-        xws = ws ? enc_alloc(h, h->ext_ws_bytes / 2) : nullptr;
+        xws = ws ? dev_alloc(h->allocs, h->ext_ws_bytes / 2) : nullptr;
     }
     if (!ws) xws = nullptr;
     if (!xws) return fail(ACEHIP_E_OOM, "enc_kv_create: device allocation failed");   // freed by enc_destroy
@@ -424,7 +416,18 @@ int acehip_enc_prefill(acehip_enc *h, const void *x, const uint8_t *kmask, int B
     if (B <= 0 || B > h->kv_B || S <= 0 || S > h->kv_cap || (int64_t)B * S > h->cfg.max_tokens)
         return fail(ACEHIP_E_ARG, "enc_prefill: B / S / B*S out of range (cache batch, capacity, max_tokens)");
     HIP_TRY(hipSetDevice(h->device));
-    return enc_forward_impl(h, x, kmask, B, S, out, stream, true);
+    return enc_run(h, x, enc_buffer_pass(h, kmask, B, S, true), out, (hipStream_t)stream);
+}
+
+// n tokens per sequence appended at cache positions [pos, pos + n) of cache rows row0 .. row0 + B − 1
+static EncPass enc_cache_pass(const uint8_t *kmask, int mask_ld, int row0, int B, int pos, int n) {
+    EncPass p{};
+    p.B = B; p.n = n; p.pos = pos; p.row0 = row0;
+    p.kv = EncPass::KV_CACHE;
+    p.att = EncPass::ATT_EXTEND;
+    p.kmask = kmask; p.mask_ld = mask_ld;
+    p.tail = EncPass::OUT_ALL_ROWS;
+    return p;
 }
 
 int acehip_enc_decode(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int B, int pos, void *out,
@@ -436,54 +439,11 @@ int acehip_enc_decode(acehip_enc *h, const void *x, const uint8_t *kmask, int ma
     if (pos < 0 || pos >= h->kv_cap) return fail(ACEHIP_E_ARG, "enc_decode: pos must be in [0, capacity)");
     if (kmask && mask_ld < pos + 1) return fail(ACEHIP_E_ARG, "enc_decode: mask_ld < pos + 1");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, cap = h->kv_cap;
-    const int H = h->cfg.heads, KV = h->cfg.kv_heads;
-    const float eps = h->cfg.eps, scale = 1.0f / sqrtf(128.0f);
-    const size_t per = (size_t)h->kv_B * KV * cap * 128;
-    int rc;
-#define RUN(e) do { if ((rc = (e))) return rc; } while (0)
-    HIP_TRY(hipMemcpyAsync(h->X, x, (size_t)B * D * 2, hipMemcpyDeviceToDevice, s));
-    RowAdd pend{};
-    for (int l = 0; l < h->L; ++l) {
-        const auto &ly = h->layers[l];
-        RUN(rmsnorm_mod(h->X, ly.ln1, nullptr, nullptr, 0, 1, h->XN, B, D, eps, s, pend));
-        pend = RowAdd{};
-        // one row per sequence: RoPE row `pos`, q compact [B][H][128], k / v into cache slot pos
-        GemmArgs q{};
-        q.A = h->XN; q.lda = D; q.W = ly.wqkv; q.ldw = D;
-        q.M = B; q.N = qd + 2 * kvd; q.K = D; q.epi = EPI_HEADPOST;
-        q.hp.B = B; q.hp.S = 1; q.hp.nq = H; q.hp.nk = KV; q.hp.nv = KV; q.hp.qw = ly.qn; q.hp.kw = ly.kn;
-        q.hp.cos = h->rope_cos + (size_t)pos * 128; q.hp.sin = h->rope_sin + (size_t)pos * 128;
-        q.hp.q = h->Qh; q.hp.S_dst_q = 1;
-        q.hp.k = h->Kc + l * per + (size_t)pos * 128; q.hp.v = h->Vc + l * per + (size_t)pos * 128;
-        q.hp.S_dst = cap; q.hp.eps = eps;
-        RUN(hgemm(h, q, s));
-        RUN(attention_decode(h->Qh, h->Kc + l * per, h->Vc + l * per, h->AO, B, H, KV, pos + 1, cap, kmask, mask_ld,
-                             scale, h->dec_ws, h->dec_ws_bytes, s));
-        GemmArgs o{};
-        o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
-        o.M = B; o.N = D; o.K = qd; o.epi = EPI_RES; o.res = h->X; o.ldr = D;
-        RUN(hgemm(h, o, s, &pend));
-        RUN(rmsnorm_mod(h->X, ly.ln2, nullptr, nullptr, 0, 1, h->XN, B, D, eps, s, pend));
-        pend = RowAdd{};
-        GemmArgs gu{};
-        gu.A = h->XN; gu.lda = D; gu.W = ly.wgu; gu.ldw = D; gu.C = h->Hb; gu.ldc = F;
-        gu.M = B; gu.N = 2 * F; gu.K = D; gu.epi = EPI_SWIGLU;
-        RUN(hgemm(h, gu, s));
-        GemmArgs dn{};
-        dn.A = h->Hb; dn.lda = F; dn.W = ly.wdown; dn.ldw = F; dn.C = h->X; dn.ldc = D;
-        dn.M = B; dn.N = D; dn.K = F; dn.epi = EPI_RES; dn.res = h->X; dn.ldr = D;
-        RUN(hgemm(h, dn, s, &pend));
-    }
-    RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, 1, (bf16_t *)out, B, D, eps, s, pend));
-#undef RUN
-    return 0;
+    EncPass p = enc_cache_pass(kmask, mask_ld, 0, B, pos, 1);   // one token, on its own attention kernel
+    p.att = EncPass::ATT_DECODE;
+    return enc_run(h, x, p, out, (hipStream_t)stream);
 }
 
-// n tokens per sequence appended at cache positions [pos, pos + n) of cache rows row0 .. row0 + B − 1:
-// acehip_enc_decode's layer loop on M = B·n rows — head-post writes q compact [B][H][n][128] and
-// k / v straight into the cache rows — with attention_extend in place of attention_decode
 int acehip_enc_extend(acehip_enc *h, const void *x, const uint8_t *kmask, int mask_ld, int row0, int B, int pos, int n,
                       void *out, void *stream) {
     if (!h || !x || !out) return fail(ACEHIP_E_ARG, "null argument");
@@ -496,50 +456,7 @@ int acehip_enc_extend(acehip_enc *h, const void *x, const uint8_t *kmask, int ma
     if ((int64_t)B * n > h->cfg.max_tokens) return fail(ACEHIP_E_ARG, "enc_extend: B*n exceeds max_tokens");
     if (kmask && mask_ld < pos + n) return fail(ACEHIP_E_ARG, "enc_extend: mask_ld < pos + n");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, cap = h->kv_cap, M = B * n;
-    const int H = h->cfg.heads, KV = h->cfg.kv_heads;
-    const float eps = h->cfg.eps, scale = 1.0f / sqrtf(128.0f);
-    const size_t per = (size_t)h->kv_B * KV * cap * 128, row_off = (size_t)row0 * KV * cap * 128;
-    int rc;
-#define RUN(e) do { if ((rc = (e))) return rc; } while (0)
-    HIP_TRY(hipMemcpyAsync(h->X, x, (size_t)M * D * 2, hipMemcpyDeviceToDevice, s));
-    RowAdd pend{};
-    for (int l = 0; l < h->L; ++l) {
-        const auto &ly = h->layers[l];
-        bf16_t *Kl = h->Kc + l * per + row_off, *Vl = h->Vc + l * per + row_off;
-        RUN(rmsnorm_mod(h->X, ly.ln1, nullptr, nullptr, 0, n, h->XN, M, D, eps, s, pend));
-        pend = RowAdd{};
-        // n rows per sequence: RoPE rows pos .. pos + n − 1, q compact, k / v into cache slots pos ..
-        GemmArgs q{};
-        q.A = h->XN; q.lda = D; q.W = ly.wqkv; q.ldw = D;
-        q.M = M; q.N = qd + 2 * kvd; q.K = D; q.epi = EPI_HEADPOST;
-        q.hp.B = B; q.hp.S = n; q.hp.nq = H; q.hp.nk = KV; q.hp.nv = KV; q.hp.qw = ly.qn; q.hp.kw = ly.kn;
-        q.hp.cos = h->rope_cos + (size_t)pos * 128; q.hp.sin = h->rope_sin + (size_t)pos * 128;
-        q.hp.q = h->Qh; q.hp.S_dst_q = n;
-        q.hp.k = Kl + (size_t)pos * 128; q.hp.v = Vl + (size_t)pos * 128;
-        q.hp.S_dst = cap; q.hp.eps = eps;
-        RUN(hgemm(h, q, s));
-        RUN(attention_extend(h->Qh, Kl, Vl, h->AO, B, H, KV, n, pos, cap, kmask, mask_ld, scale, h->ext_ws,
-                             h->ext_ws_bytes, s));
-        GemmArgs o{};
-        o.A = h->AO; o.lda = qd; o.W = ly.wo; o.ldw = qd; o.C = h->X; o.ldc = D;
-        o.M = M; o.N = D; o.K = qd; o.epi = EPI_RES; o.res = h->X; o.ldr = D;
-        RUN(hgemm(h, o, s, &pend));
-        RUN(rmsnorm_mod(h->X, ly.ln2, nullptr, nullptr, 0, n, h->XN, M, D, eps, s, pend));
-        pend = RowAdd{};
-        GemmArgs gu{};
-        gu.A = h->XN; gu.lda = D; gu.W = ly.wgu; gu.ldw = D; gu.C = h->Hb; gu.ldc = F;
-        gu.M = M; gu.N = 2 * F; gu.K = D; gu.epi = EPI_SWIGLU;
-        RUN(hgemm(h, gu, s));
-        GemmArgs dn{};
-        dn.A = h->Hb; dn.lda = F; dn.W = ly.wdown; dn.ldw = F; dn.C = h->X; dn.ldc = D;
-        dn.M = M; dn.N = D; dn.K = F; dn.epi = EPI_RES; dn.res = h->X; dn.ldr = D;
-        RUN(hgemm(h, dn, s, &pend));
-    }
-    RUN(rmsnorm_mod(h->X, h->norm, nullptr, nullptr, 0, n, (bf16_t *)out, M, D, eps, s, pend));
-#undef RUN
-    return 0;
+    return enc_run(h, x, enc_cache_pass(kmask, mask_ld, row0, B, pos, n), out, (hipStream_t)stream);
 }
 
 int acehip_fsq_quantize(const void *z, int ldz, int M, const int *levels, int n_levels, void *codes, int ldc,
