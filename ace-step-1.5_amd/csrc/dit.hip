@@ -14,111 +14,13 @@
 //   proj_out ConvT  [D][64][2]   → [2·64][D] so the GEMM output [S][128] is
 //            the de-patchified [2S][64] sequence in place
 //   scale_shift_tables of all layers contiguous → one modulation launch
-#include <unistd.h>
-#include <map>
-#include <mutex>
-#include <cmath>
-#include <vector>
-#include <cstring>
-
-#include "layer_args.h"
-#include "../../include/acehip.h"
+//
+// The handle and the state-dict names are in dit_handle.h, the loader in weights.h, the fp32
+// parity mode in dit_f32.hip; the library's error state and the stand-alone kernel entry
+// points are in abi.hip.
+#include "dit_handle.h"
 
 using namespace acehip;
-
-namespace {
-
-enum PackKind { P_COPY, P_GU_GATE, P_GU_UP, P_PROJ_IN, P_PROJ_OUT_W, P_PROJ_OUT_B,
-                // fp32 parity mode: fp32 destinations, reference layouts except the patch convs
-                P_F32, P_F32_PROJ_IN, P_F32_PROJ_OUT_W, P_F32_PROJ_OUT_B };
-
-struct Slot {
-    bf16_t *dst = nullptr;
-    std::vector<int64_t> shape;
-    PackKind kind = P_COPY;
-    bool set = false;
-    float *dst_f32 = nullptr;
-};
-
-}  // namespace
-
-struct acehip_dit {
-    int device = 0;
-    acehip_dit_cfg cfg{};
-    std::vector<uint8_t> sliding;
-    int D = 0, F = 0, qd = 0, kvd = 0, L = 0;
-    bool finalized = false, have_cond = false;
-    int cond_Bc = 0, cond_Lenc = 0;
-
-    std::vector<void *> allocs;
-    std::map<std::string, Slot> slots;
-
-    // weights
-    bf16_t *tables = nullptr;   // [L][6][D]
-    struct Layer {
-        bf16_t *n_sa, *n_ca, *n_mlp, *wqkv, *wo, *qn, *kn, *cqn, *ckn, *wcq, *wckv, *wco, *wgu, *wdown;
-    };
-    std::vector<Layer> layers;
-    bf16_t *sst_out, *win, *bin, *wce, *bce, *norm_out, *wout, *bout;
-    bf16_t *te_l1[2], *te_b1[2], *te_l2[2], *te_b2[2], *te_tp[2], *te_btp[2];
-    float *freqs = nullptr;          // [128] sinusoid frequencies
-    float *inv_freq_host = nullptr;  // optional override, [hd/2]
-    std::vector<float> inv_freq_override;
-    bf16_t *attn_ws = nullptr;  // attention tail-split workspace (attention_ws_bytes())
-    bf16_t *rope_cos = nullptr, *rope_sin = nullptr;   // [max_S][hd]
-
-    // workspace
-    bf16_t *X, *XN, *Qh, *Kh, *Vh, *AO, *Hb, *Xin, *O2;
-    bf16_t *emb[2], *h1, *temb_e[2], *proj_e[2], *temb, *proj, *mod, *mod_out;
-    bf16_t *Kc, *Vc, *E, *KVtmp;
-    int kv_group = 1;                  // layers per cross-K/V GEMM at set_condition (KVtmp holds that many)
-    bf16_t *wckv_all = nullptr;        // every layer's cross K/V projection, [L][2·kvd][D] (one GEMM)
-    bf16_t *gemv_act = nullptr;        // 16 × D: bf16(silu(x)) rows of the timestep MLPs (gemv_small)
-    // CFG null rows (acehip_dit_set_uniform_rows): batch rows >= uniform_from have an
-    // encoder sequence that is one vector repeated, so their cross-attention is the
-    // constant V row and their cross-O output the per-layer constant cnull[l]
-    int uniform_from = 1 << 30;
-    bf16_t *cnull = nullptr, *vnull = nullptr;   // [L][D], [q_dim]
-    // timestep MLP outputs of a whole schedule (acehip_dit_set_timesteps): row i = step i's
-    // temb [D] and proj [6D]; ts_scratch holds the batched MLP intermediates
-    int ts_n = 0, ts_cap = 0;
-    bf16_t *ts_temb = nullptr, *ts_proj = nullptr, *ts_scratch = nullptr;
-    bf16_t *tmp;   // weight staging (fp32 → bf16 casts, host repacks)
-    void *gemm_ws = nullptr;   // split-K partials for small-M GEMMs (short songs / turbo)
-    size_t tmp_elems = 0;
-
-    // optional per-kernel event timing (acehip_dit_profile)
-    static constexpr int NKIND = 7, NPAIR = 16384;
-    bool prof = false;
-    unsigned prof_mask = 0x7f;         // kinds recorded while profiling (acehip_dit_profile_kinds)
-    std::vector<hipEvent_t> ev;        // 2·NPAIR events
-    std::vector<int> ev_kind;          // kind of each recorded pair
-    int ev_used = 0;
-
-    // HIP graph of the forward's pointer-independent middle (acehip_dit_set_graph): the
-    // timestep MLPs, modulation, proj_in and the layer stack read and write only handle
-    // buffers, so one capture per (Bc, S, Lenc, uniform_from) replays for every step
-    bool graph_on = false;
-    hipStream_t cap_stream = nullptr;
-    hipGraphExec_t gexec = nullptr;
-    int gkey[6] = {-1, -1, -1, -1, -1, -1};
-
-    // fp32 parity mode (acehip_dit_cfg.fp32): fp32 weights and workspace,
-    // the kernels of f32.hip; the bf16 buffers above are not allocated
-    bool f32 = false;
-    struct F32 {
-        struct Layer {
-            float *n_sa, *n_ca, *n_mlp, *wqkv, *wo, *qn, *kn, *cqn, *ckn, *wcq, *wckv, *wco, *wg, *wu, *wdown;
-        };
-        std::vector<Layer> layers;
-        float *tables, *sst_out, *win, *bin, *wce, *bce, *norm_out, *wout, *bout;
-        float *te_l1[2], *te_b1[2], *te_l2[2], *te_b2[2], *te_tp[2], *te_btp[2];
-        float *rope_cos, *rope_sin;
-        float *X, *XN, *QKV, *Qh, *Kh, *Vh, *AO, *G, *U, *Hb, *Xin, *O2;
-        float *emb[2], *h1, *temb_e[2], *proj_e[2], *temb, *proj, *mod, *mod_out;
-        float *Kc, *Vc, *E, *KVtmp;
-    } f{};
-};
 
 static int forward_body(acehip_dit *h, int Bc, int S, bool dup, bool ts_cached, hipStream_t s,
                         const acehip_attn_capture *cap = nullptr);
@@ -127,71 +29,8 @@ static int timestep_mlps(acehip_dit *h, const bf16_t *const emb[2], int rows, bf
 static int forward_bf16(acehip_dit *h, const void *xt, const void *ctx, int Bx, const float *t, const float *t_r,
                         int t_stride, int step, int Bc, int T, void *vt_out, hipStream_t s,
                         const acehip_attn_capture *cap = nullptr);
-static int create_f32(acehip_dit *h);
-static int set_weight_f32(acehip_dit *h, Slot &s, const void *ptr, int dtype, int64_t n, int on_device);
-static int build_rope_f32(acehip_dit *h);
-static int set_condition_f32(acehip_dit *h, const float *enc, int Bc, int Lenc, hipStream_t s);
-static int forward_f32(acehip_dit *h, const float *xt, const float *ctx, int Bx, const float *t, const float *t_r,
-                       int t_stride, int Bc, int T, float *vt_out, hipStream_t s,
-                       const acehip_attn_capture *cap = nullptr);
-
-namespace {
-
-thread_local std::string g_err;
-
-void add_slot(acehip_dit *h, const std::string &name, bf16_t *dst, std::vector<int64_t> shape,
-              PackKind kind = P_COPY) {
-    Slot s;
-    s.dst = dst;
-    s.shape = std::move(shape);
-    s.kind = kind;
-    h->slots[name] = s;
-}
-
-int64_t numel(const std::vector<int64_t> &s) {
-    int64_t n = 1;
-    for (auto v : s) n *= v;
-    return n;
-}
-
-// host-side bf16 rounding (same as device f2bf)
-inline bf16_t hf2bf(float f) { return f2bf(f); }
-
-// record an event pair around `launch` when profiling is on
-template <class F>
-int timed(acehip_dit *h, int kind, hipStream_t s, F &&launch) {
-    if (!h->prof || !((h->prof_mask >> kind) & 1u) || h->ev_used >= acehip_dit::NPAIR) return launch();
-    const int i = h->ev_used++;
-    h->ev_kind[i] = kind;
-    if (kind == 0) {
-        // the SwiGLU GEMM (the bench's roofline kernel, timed inside the measured song): the
-        // events ride on its launches (gemm_ext_events) instead of two event packets that
-        // would idle the GPU ≈ 5.6 µs each; a path without launch events drops the sample
-        gemm_ext_events(h->ev[2 * i], h->ev[2 * i + 1]);
-        const int rc = launch();
-        if (!gemm_ext_events(nullptr, nullptr)) h->ev_kind[i] = -1;
-        return rc;
-    }
-    HIP_TRY(hipEventRecord(h->ev[2 * i], s));
-    const int rc = launch();
-    HIP_TRY(hipEventRecord(h->ev[2 * i + 1], s));
-    return rc;
-}
-
-}  // namespace
-
-namespace acehip {
-void set_error(const std::string &msg) { g_err = msg; }
-int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-}  // namespace acehip
 
 extern "C" {
-
-int acehip_get_version(void) { return ACEHIP_VERSION; }
-const char *acehip_last_error(void) { return g_err.c_str(); }
 
 int acehip_dit_create(int device, const acehip_dit_cfg *cfg, acehip_dit **out) {
     if (!cfg || !out) return fail(ACEHIP_E_ARG, "dit_create: null argument");
@@ -215,7 +54,7 @@ int acehip_dit_create(int device, const acehip_dit_cfg *cfg, acehip_dit **out) {
     if (cfg->fp32) {
         h->f32 = true;
         h->graph_on = false;
-        const int rc = create_f32(h);
+        const int rc = dit_create_f32(h);
         if (rc) {
             const std::string e = acehip_last_error();
             acehip_dit_destroy(h);
@@ -241,55 +80,20 @@ int acehip_dit_create(int device, const acehip_dit_cfg *cfg, acehip_dit **out) {
         ly.wcq = A((size_t)qd * D); ly.wckv = h->wckv_all ? h->wckv_all + (size_t)i * 2 * kvd * D : nullptr;
         ly.wco = A((size_t)D * qd);
         ly.wgu = A((size_t)2 * F * D); ly.wdown = A((size_t)D * F);
-        if (!ok) break;
-        const std::string p = "layers." + std::to_string(i);
-        add_slot(h, p + ".scale_shift_table", h->tables + (size_t)i * 6 * D, {1, 6, D});
-        add_slot(h, p + ".self_attn_norm.weight", ly.n_sa, {D});
-        add_slot(h, p + ".cross_attn_norm.weight", ly.n_ca, {D});
-        add_slot(h, p + ".mlp_norm.weight", ly.n_mlp, {D});
-        add_slot(h, p + ".self_attn.q_proj.weight", ly.wqkv, {qd, D});
-        add_slot(h, p + ".self_attn.k_proj.weight", ly.wqkv + (size_t)qd * D, {kvd, D});
-        add_slot(h, p + ".self_attn.v_proj.weight", ly.wqkv + (size_t)(qd + kvd) * D, {kvd, D});
-        add_slot(h, p + ".self_attn.o_proj.weight", ly.wo, {D, qd});
-        add_slot(h, p + ".self_attn.q_norm.weight", ly.qn, {128});
-        add_slot(h, p + ".self_attn.k_norm.weight", ly.kn, {128});
-        add_slot(h, p + ".cross_attn.q_proj.weight", ly.wcq, {qd, D});
-        add_slot(h, p + ".cross_attn.k_proj.weight", ly.wckv, {kvd, D});
-        add_slot(h, p + ".cross_attn.v_proj.weight", ly.wckv + (size_t)kvd * D, {kvd, D});
-        add_slot(h, p + ".cross_attn.o_proj.weight", ly.wco, {D, qd});
-        add_slot(h, p + ".cross_attn.q_norm.weight", ly.cqn, {128});
-        add_slot(h, p + ".cross_attn.k_norm.weight", ly.ckn, {128});
-        add_slot(h, p + ".mlp.gate_proj.weight", ly.wgu, {F, D}, P_GU_GATE);
-        add_slot(h, p + ".mlp.up_proj.weight", ly.wgu, {F, D}, P_GU_UP);
-        add_slot(h, p + ".mlp.down_proj.weight", ly.wdown, {D, F});
     }
     h->sst_out = A(2 * D); h->win = A((size_t)D * 384); h->bin = A(D);
     h->wce = A((size_t)D * D); h->bce = A(D); h->norm_out = A(D);
     h->wout = A((size_t)128 * D); h->bout = A(128);
-    const char *te_names[2] = {"time_embed", "time_embed_r"};
     for (int e = 0; e < 2; ++e) {
         h->te_l1[e] = A((size_t)D * 256); h->te_b1[e] = A(D);
         h->te_l2[e] = A((size_t)D * D); h->te_b2[e] = A(D);
         h->te_tp[e] = A((size_t)6 * D * D); h->te_btp[e] = A(6 * D);
-        if (!ok) break;
-        const std::string p = te_names[e];
-        add_slot(h, p + ".linear_1.weight", h->te_l1[e], {D, 256});
-        add_slot(h, p + ".linear_1.bias", h->te_b1[e], {D});
-        add_slot(h, p + ".linear_2.weight", h->te_l2[e], {D, D});
-        add_slot(h, p + ".linear_2.bias", h->te_b2[e], {D});
-        add_slot(h, p + ".time_proj.weight", h->te_tp[e], {6 * D, D});
-        add_slot(h, p + ".time_proj.bias", h->te_btp[e], {6 * D});
     }
-    if (ok) {
-        add_slot(h, "scale_shift_table", h->sst_out, {1, 2, D});
-        add_slot(h, "proj_in.1.weight", h->win, {D, 192, 2}, P_PROJ_IN);
-        add_slot(h, "proj_in.1.bias", h->bin, {D});
-        add_slot(h, "condition_embedder.weight", h->wce, {D, D});
-        add_slot(h, "condition_embedder.bias", h->bce, {D});
-        add_slot(h, "norm_out.weight", h->norm_out, {D});
-        add_slot(h, "proj_out.1.weight", h->wout, {D, 64, 2}, P_PROJ_OUT_W);
-        add_slot(h, "proj_out.1.bias", h->bout, {64}, P_PROJ_OUT_B);
-    }
+    // bf16: gate and up interleaved into one SwiGLU operand; the cross k|v slots point into wckv_all
+    if (ok)
+        register_dit_weights(h->weights, *h, L, D, F, qd, kvd, [](const acehip_dit::Layer &ly) {
+            return GateUpDst<bf16_t>{ly.wgu, Pack::GU_GATE, ly.wgu, Pack::GU_UP};
+        });
     // workspace
     const size_t S = cfg->max_S, Bc = cfg->max_Bc, M = S * Bc, Le = cfg->max_Lenc;
     h->X = A(M * D); h->XN = A(M * D);
@@ -349,105 +153,19 @@ int acehip_dit_set_weight(acehip_dit *h, const char *name, const void *ptr, int 
     if (nm == "_timestep_freqs" || nm == "_rope_inv_freq") {
         // optional overrides computed by the caller's torch (exact reference constants), fp32
         if (dtype != ACEHIP_F32) return fail(ACEHIP_E_ARG, nm + ": fp32 required");
-        const int n = (int)shape[0];
-        std::vector<float> v(n);
-        HIP_TRY(hipMemcpy(v.data(), ptr, n * 4, on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        if (nm == "_timestep_freqs") {
-            if (n != 128) return fail(ACEHIP_E_ARG, "_timestep_freqs must have 128 entries");
-            HIP_TRY(hipMemcpy(h->freqs, v.data(), 512, hipMemcpyHostToDevice));
-        } else {
-            if (n != h->cfg.head_dim / 2) return fail(ACEHIP_E_ARG, "_rope_inv_freq size");
-            h->inv_freq_override = v;
-        }
+        const bool freqs = nm == "_timestep_freqs";
+        if (freqs && shape[0] != 128) return fail(ACEHIP_E_ARG, "_timestep_freqs must have 128 entries");
+        if (!freqs && shape[0] != h->cfg.head_dim / 2) return fail(ACEHIP_E_ARG, "_rope_inv_freq size");
+        std::vector<float> v;
+        if (int rc = fetch_host_f32(ptr, dtype, shape[0], on_device, v)) return rc;
+        if (freqs) HIP_TRY(hipMemcpy(h->freqs, v.data(), 512, hipMemcpyHostToDevice));
+        else h->inv_freq_override = v;
         return 0;
     }
     if (nm == "rotary_emb.inv_freq") return 0;  // non-persistent buffer; recomputed
-    auto it = h->slots.find(nm);
-    if (it == h->slots.end()) return fail(ACEHIP_E_NAME, "dit_set_weight: unknown weight " + nm);
-    Slot &s = it->second;
-    std::vector<int64_t> sh(shape, shape + ndim);
-    if (sh != s.shape) {
-        std::string e = "dit_set_weight: shape mismatch for " + nm + " got [";
-        for (auto v : sh) e += std::to_string(v) + ",";
-        e += "] want [";
-        for (auto v : s.shape) e += std::to_string(v) + ",";
-        return fail(ACEHIP_E_ARG, e + "]");
-    }
-    const int64_t n = numel(sh);
-    if (dtype != ACEHIP_F32 && dtype != ACEHIP_BF16) return fail(ACEHIP_E_ARG, "dtype");
-    if (h->f32) return set_weight_f32(h, s, ptr, dtype, n, on_device);
-    // bring to a contiguous bf16 device source
-    const bf16_t *src = nullptr;
-    std::vector<bf16_t> hb;
-    if (s.kind == P_PROJ_IN || s.kind == P_PROJ_OUT_W || s.kind == P_PROJ_OUT_B) {
-        // small: repack on host
-        std::vector<float> f(n);
-        if (dtype == ACEHIP_F32) {
-            HIP_TRY(hipMemcpy(f.data(), ptr, n * 4, on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        } else {
-            std::vector<bf16_t> b(n);
-            HIP_TRY(hipMemcpy(b.data(), ptr, n * 2, on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-            for (int64_t i = 0; i < n; ++i) f[i] = bf2f(b[i]);
-        }
-        hb.resize(s.kind == P_PROJ_OUT_B ? 128 : n);
-        if (s.kind == P_PROJ_IN) {         // [D][192][2] → [D][k*192 + c]
-            const int64_t D = sh[0];
-            for (int64_t o = 0; o < D; ++o)
-                for (int c = 0; c < 192; ++c)
-                    for (int k = 0; k < 2; ++k) hb[o * 384 + k * 192 + c] = hf2bf(f[(o * 192 + c) * 2 + k]);
-        } else if (s.kind == P_PROJ_OUT_W) {   // [D][64][2] → [k*64 + o][D]
-            const int64_t D = sh[0];
-            for (int64_t c = 0; c < D; ++c)
-                for (int o = 0; o < 64; ++o)
-                    for (int k = 0; k < 2; ++k) hb[(k * 64 + o) * D + c] = hf2bf(f[(c * 64 + o) * 2 + k]);
-        } else {                               // bias [64] → [k*64 + o]
-            for (int k = 0; k < 2; ++k)
-                for (int o = 0; o < 64; ++o) hb[k * 64 + o] = hf2bf(f[o]);
-        }
-        HIP_TRY(hipMemcpy(s.dst, hb.data(), hb.size() * 2, hipMemcpyHostToDevice));
-        s.set = true;
-        return 0;
-    }
-    if (dtype == ACEHIP_F32) {
-        // cast through the staging buffer in chunks
-        // tmp holds tmp_elems floats (4·tmp_elems bytes)
-        const float *fsrc = (const float *)ptr;
-        float *fstage = (float *)h->tmp;
-        if (s.kind == P_COPY) {
-            // chunked cast straight into the destination
-            const int64_t chunk = (int64_t)h->tmp_elems;
-            for (int64_t off = 0; off < n; off += chunk) {
-                const int64_t c = std::min(chunk, n - off);
-                HIP_TRY(hipMemcpy(fstage, fsrc + off, c * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-                int rc = cast_f32_bf16(fstage, s.dst + off, c, 0);
-                if (rc) return rc;
-                HIP_TRY(hipDeviceSynchronize());
-            }
-            s.set = true;
-            return 0;
-        }
-        if ((size_t)n * 6 > h->tmp_elems * 4) return fail(ACEHIP_E_ARG, "fp32 weight too large for staging; pass bf16");
-        HIP_TRY(hipMemcpy(fstage, fsrc, n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-        bf16_t *b16 = h->tmp + n * 2;   // bf16 copy right after the fp32 staging
-        int rc = cast_f32_bf16(fstage, b16, n, 0);
-        if (rc) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-        src = b16;
-    } else {
-        if (s.kind == P_COPY) {
-            HIP_TRY(hipMemcpy(s.dst, ptr, n * 2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            s.set = true;
-            return 0;
-        }
-        src = (const bf16_t *)ptr;
-    }
-    const hipMemcpyKind kind = (dtype == ACEHIP_F32 || on_device) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (s.kind == P_GU_GATE || s.kind == P_GU_UP) {
-        if (int rc = pack_gate_up(s.dst, src, sh[0], sh[1], s.kind == P_GU_UP, kind)) return rc;
-        s.set = true;
-        return 0;
-    }
-    return fail(ACEHIP_E_ARG, "dit_set_weight: unhandled pack kind");
+    WeightSlot *s = nullptr;
+    if (int rc = h->weights.find_checked(nm, ndim, shape, "dit_set_weight", s)) return rc;
+    return load_weight(*s, "dit_set_weight", nm, ptr, dtype, on_device, Staging{h->tmp, h->tmp_elems * 4});
 }
 
 // Buffers of acehip_dit_set_timesteps for `cap` steps: allocated at finalize for kTsCap
@@ -474,12 +192,10 @@ int acehip_dit_finalize(acehip_dit *h) {
     if (!h) return fail(ACEHIP_E_ARG, "null handle");
     HIP_TRY(hipSetDevice(h->device));
     if (h->gexec) { HIP_TRY(hipGraphExecDestroy(h->gexec)); h->gexec = nullptr; }   // re-capture
-    std::string missing;
-    for (auto &kv : h->slots)
-        if (!kv.second.set) missing += kv.first + " ";
-    if (!missing.empty()) return fail(ACEHIP_E_STATE, "dit_finalize: missing weights: " + missing.substr(0, 400));
+    int rc = h->weights.missing("dit_finalize");
+    if (rc) return rc;
     if (h->F % 32) return fail(ACEHIP_E_ARG, "intermediate must be a multiple of 32");
-    int rc = h->f32 ? build_rope_f32(h)
+    rc = h->f32 ? dit_build_rope_f32(h)
                     : build_rope_tables(h->cfg.head_dim, h->cfg.max_S, h->cfg.rope_theta, h->inv_freq_override,
                                         h->rope_cos, h->rope_sin);
     if (rc) return rc;
@@ -496,7 +212,7 @@ int acehip_dit_set_condition(acehip_dit *h, const void *enc, int Bc, int Lenc, v
         return fail(ACEHIP_E_ARG, "set_condition: Bc/Lenc out of range");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (h->f32) return set_condition_f32(h, (const float *)enc, Bc, Lenc, s);
+    if (h->f32) return dit_set_condition_f32(h, (const float *)enc, Bc, Lenc, s);
     const int D = h->D, kvd = h->kvd, M = Bc * Lenc;
     int rc = hgemm(h, lin_store((const bf16_t *)enc, D, h->wce, h->E, D, M, D, D, h->bce), s);
     if (rc) return rc;
@@ -566,7 +282,7 @@ int acehip_dit_forward(acehip_dit *h, const void *xt, const void *ctx, int Bx, c
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->f32)
-        return forward_f32(h, (const float *)xt, (const float *)ctx, Bx, t, t_r, t_stride, Bc, T, (float *)vt_out, s);
+        return dit_forward_f32(h, (const float *)xt, (const float *)ctx, Bx, t, t_r, t_stride, Bc, T, (float *)vt_out, s);
     return forward_bf16(h, xt, ctx, Bx, t, t_r, t_stride, -1, Bc, T, vt_out, s);
 }
 
@@ -604,7 +320,7 @@ int acehip_dit_forward_capture(acehip_dit *h, const void *xt, const void *ctx, i
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->f32)
-        return forward_f32(h, (const float *)xt, (const float *)ctx, Bx, t, t_r, t_stride, Bc, T, (float *)vt_out, s,
+        return dit_forward_f32(h, (const float *)xt, (const float *)ctx, Bx, t, t_r, t_stride, Bc, T, (float *)vt_out, s,
                            cap);
     return forward_bf16(h, xt, ctx, Bx, t, t_r, t_stride, -1, Bc, T, vt_out, s, cap);
 }
@@ -738,23 +454,6 @@ static int timestep_mlps(acehip_dit *h, const bf16_t *const emb[2], int rows, bf
     RUN(add_bf16(temb_e[0], temb_e[1], temb, (int64_t)rows * D, s));
     RUN(add_bf16(proj_e[0], proj_e[1], proj, (int64_t)rows * 6 * D, s));
     return 0;
-}
-
-// the capture's entries of layer l (heads + their output slots); returns how many
-static int capture_layer(const acehip_attn_capture *cap, int l, AttnProbsSel &sel) {
-    sel.n = 0;
-    for (int i = 0; i < cap->n; ++i)
-        if (cap->layer[i] == l) {
-            sel.head[sel.n] = (int16_t)cap->head[i];
-            sel.slot[sel.n] = (int16_t)i;
-            ++sel.n;
-        }
-    return sel.n;
-}
-static int capture_last_layer(const acehip_attn_capture *cap) {
-    int last = 0;
-    for (int i = 0; i < cap->n; ++i) last = std::max(last, cap->layer[i]);
-    return last;
 }
 
 // cap != null (acehip_dit_forward_capture): the selected heads' softmax rows of each captured
@@ -919,516 +618,4 @@ int acehip_dit_destroy(acehip_dit *h) {
     return 0;
 }
 
-static int sampler_dtype(int dtype, bool *f32) {
-    if (dtype != ACEHIP_BF16 && dtype != ACEHIP_F32) return fail(ACEHIP_E_ARG, "sampler: dtype");
-    *f32 = dtype == ACEHIP_F32;
-    return 0;
-}
-
-int acehip_sampler_apg_euler(const void *vt, void *xt, void *ra, int B, int T, int C, float guidance,
-                             float dt, int apply_cfg, int first_step, int out_mode, int dtype, void *stream) {
-    if (!vt || !xt || (apply_cfg > 0 && !ra)) return fail(ACEHIP_E_ARG, "null argument");
-    bool f32;
-    if (int rc = sampler_dtype(dtype, &f32)) return rc;
-    return apg_euler(vt, xt, ra, B, T, C, guidance, dt, apply_cfg, first_step, out_mode, f32, (hipStream_t)stream);
-}
-
-int acehip_sampler_adg_euler(const void *vt, void *xt, int B, int T, int C, float guidance, float sigma,
-                             float dt, int out_mode, int dtype, void *stream) {
-    if (!vt || !xt) return fail(ACEHIP_E_ARG, "null argument");
-    bool f32;
-    if (int rc = sampler_dtype(dtype, &f32)) return rc;
-    return adg_euler(vt, xt, B, T, C, guidance, sigma, dt, out_mode, f32, (hipStream_t)stream);
-}
-
-int acehip_sampler_axpy(const void *vt, void *xt, int64_t n, float s, int dtype, void *stream) {
-    if (!vt || !xt) return fail(ACEHIP_E_ARG, "null argument");
-    bool f32;
-    if (int rc = sampler_dtype(dtype, &f32)) return rc;
-    return axpy(vt, xt, n, s, f32, (hipStream_t)stream);
-}
-
-int acehip_gemm_bf16(const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M, int N,
-                     int K, const void *bias, void *stream) {
-    GemmArgs g{};
-    g.A = (const bf16_t *)A; g.lda = lda; g.W = (const bf16_t *)W; g.ldw = ldw;
-    g.C = (bf16_t *)C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.epi = EPI_STORE;
-    g.bias = (const bf16_t *)bias;
-    return gemm(g, (hipStream_t)stream);
-}
-
-// lazily allocated split-K workspace of the standalone kernel entry points (one per device)
-static std::mutex g_abi_ws_mu;
-static void *abi_gemm_ws() {
-    static std::map<int, void *> by_dev;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_abi_ws_mu);
-    void *&ws = by_dev[dev];
-    if (!ws && hipMalloc(&ws, GEMM_WS_BYTES) != hipSuccess) ws = nullptr;
-    return ws;
-}
-
-int acehip_gemm_bf16_ex(const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M, int N,
-                        int K, const void *bias, int epi, int variant, void *stream) {
-    GemmArgs g{};
-    g.A = (const bf16_t *)A; g.lda = lda; g.W = (const bf16_t *)W; g.ldw = ldw;
-    g.C = (bf16_t *)C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.bias = (const bf16_t *)bias;
-    if (epi == 2) { g.epi = EPI_RES; g.res = (const bf16_t *)C; g.ldr = ldc; }
-    else if (epi == 3) g.epi = EPI_SWIGLU;   // W rows packed [32 gate; 32 up] per 64-row panel, C[M][N/2]
-    else if (epi == 0) g.epi = EPI_STORE;
-    else return fail(ACEHIP_E_ARG, "gemm_ex: epilogue");
-    if (M <= 0 || N % 128 || K % 64) return fail(ACEHIP_E_ARG, "gemm_ex: shape");
-    if (variant < 0) {   // production dispatch (split-K for small grids)
-        g.ws = abi_gemm_ws();
-        g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
-        return gemm(g, (hipStream_t)stream);
-    }
-    return gemm_variant(g, variant, (hipStream_t)stream);
-}
-
-// residual-epilogue GemmArgs of the two test entry points below (gate == null: EPI_RES)
-static int res_gemm_args(GemmArgs &g, const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M,
-                         int N, int K, const void *res, int ldr, const void *gate, int64_t gate_bstride,
-                         int rows_per_batch) {
-    if (!A || !W || !C || !res) return fail(ACEHIP_E_ARG, "gemm_res: null argument");
-    if (M <= 0 || N % 128 || K % 64 || K <= 0) return fail(ACEHIP_E_ARG, "gemm_res: shape");
-    if ((lda | ldw | ldc | ldr) % 8 || lda < K || ldw < K || ldc < N || ldr < N)
-        return fail(ACEHIP_E_ARG, "gemm_res: leading dimensions");
-    if (gate && (rows_per_batch <= 0 || gate_bstride % 8)) return fail(ACEHIP_E_ARG, "gemm_res: gate");
-    g.A = (const bf16_t *)A; g.lda = lda; g.W = (const bf16_t *)W; g.ldw = ldw;
-    g.C = (bf16_t *)C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.res = (const bf16_t *)res; g.ldr = ldr;
-    g.epi = gate ? EPI_GATED_RES : EPI_RES;
-    g.gate = (const bf16_t *)gate; g.gate_bstride = gate_bstride; g.rows_per_batch = gate ? rows_per_batch : 0;
-    return 0;
-}
-
-int acehip_gemm_res_bf16(const void *A, int lda, const void *W, int ldw, void *C, int ldc, int M, int N, int K,
-                         const void *res, int ldr, const void *gate, int64_t gate_bstride, int rows_per_batch,
-                         int variant, void *stream) {
-    GemmArgs g{};
-    if (int rc = res_gemm_args(g, A, lda, W, ldw, C, ldc, M, N, K, res, ldr, gate, gate_bstride, rows_per_batch))
-        return rc;
-    if (variant < 0) {   // production dispatch (split-K for small grids)
-        g.ws = abi_gemm_ws();
-        g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
-        return gemm(g, (hipStream_t)stream);
-    }
-    return gemm_variant(g, variant, (hipStream_t)stream);
-}
-
-int acehip_gemm_res_norm_bf16(const void *A, int lda, const void *W, int ldw, void *X, int M, int D, int K,
-                              const void *gate, int64_t gate_bstride, int rows_per_batch, int defer,
-                              const void *w, const void *shift, const void *scale, int64_t mod_bstride, void *out,
-                              int M_norm, float eps, const void *v, int from, int *deferred, void *stream) {
-    if (!w || !out || !deferred) return fail(ACEHIP_E_ARG, "gemm_res_norm: null argument");
-    if (M_norm < M || (v && (from < M || from > M_norm))) return fail(ACEHIP_E_ARG, "gemm_res_norm: rows");
-    // what rmsnorm_mod would refuse, before the GEMM has written X
-    if (D % 256 || D > 4096) return fail(ACEHIP_E_ARG, "gemm_res_norm: D must be a multiple of 256, <= 4096");
-    if ((shift == nullptr) != (scale == nullptr)) return fail(ACEHIP_E_ARG, "gemm_res_norm: shift/scale");
-    if ((gate || scale) && rows_per_batch <= 0) return fail(ACEHIP_E_ARG, "gemm_res_norm: rows_per_batch");
-    *deferred = 0;
-    GemmArgs g{};
-    if (int rc = res_gemm_args(g, A, lda, W, ldw, X, D, M, D, K, X, D, gate, gate_bstride, rows_per_batch)) return rc;
-    g.ws = abi_gemm_ws();
-    g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
-    RowAdd ra{};
-    if (int rc = gemm(g, (hipStream_t)stream, defer ? &ra : nullptr)) return rc;
-    *deferred = ra.part != nullptr;
-    if (v) {
-        ra.xw = (bf16_t *)X;
-        ra.v = (const bf16_t *)v;
-        ra.from = from;
-    }
-    return rmsnorm_mod((const bf16_t *)X, (const bf16_t *)w, (const bf16_t *)shift, (const bf16_t *)scale,
-                       mod_bstride, rows_per_batch, (bf16_t *)out, M_norm, D, eps, (hipStream_t)stream, ra);
-}
-
-int acehip_rmsnorm_bf16(const void *x, const void *w, const void *shift, const void *scale,
-                        int64_t mod_bstride, int rows_per_batch, void *out, int M, int D, float eps,
-                        int rows_per_wave, void *stream) {
-    if (!x || !w || !out) return fail(ACEHIP_E_ARG, "null argument");
-    if (rows_per_wave == 3 || rows_per_wave > 4 || (rows_per_wave < 0 && rows_per_wave != -2 && rows_per_wave != -4))
-        return fail(ACEHIP_E_ARG, "rows_per_wave");
-    return rmsnorm_mod((const bf16_t *)x, (const bf16_t *)w, (const bf16_t *)shift, (const bf16_t *)scale,
-                       mod_bstride, rows_per_batch, (bf16_t *)out, M, D, eps, (hipStream_t)stream, RowAdd{},
-                       rows_per_wave);
-}
-
-int acehip_gemm_headpost_bf16(const void *A, int lda, const void *W, int K, int B, int S, int nq, int nk,
-                              int nv, const void *qw, const void *kw, const void *cos, const void *sin,
-                              float eps, void *q, void *k, void *v, void *stream) {
-    if (!A || !W) return fail(ACEHIP_E_ARG, "null argument");
-    if ((nq && !q) || (nk && !k) || (nv && !v)) return fail(ACEHIP_E_ARG, "missing head output");
-    if (B * S <= 0 || K % 64 || K <= 0) return fail(ACEHIP_E_ARG, "gemm_headpost: shape");
-    GemmArgs g = lin_headpost((const bf16_t *)A, lda, (const bf16_t *)W, K, B, S, nq, nk, nv, (const bf16_t *)qw,
-                              (const bf16_t *)kw, (const bf16_t *)cos, (const bf16_t *)sin, eps,
-                              HeadDst{(bf16_t *)q, (bf16_t *)k, (bf16_t *)v, S, 0});
-    g.ws = abi_gemm_ws();
-    g.ws_bytes = g.ws ? GEMM_WS_BYTES : 0;
-    return gemm(g, (hipStream_t)stream);
-}
-
-// lazily allocated Q scratch of acehip_cross_attn_bf16's two-launch path (one per device, grown on demand)
-static bf16_t *abi_cross_q(size_t bytes) {
-    static std::map<int, std::pair<void *, size_t>> by_dev;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_abi_ws_mu);
-    auto &e = by_dev[dev];
-    if (e.second < bytes) {
-        if (e.first) {
-            (void)hipDeviceSynchronize();
-            (void)hipFree(e.first);
-        }
-        e = {nullptr, 0};
-        if (hipMalloc(&e.first, bytes) != hipSuccess) return nullptr;
-        e.second = bytes;
-    }
-    return (bf16_t *)e.first;
-}
-
-int acehip_cross_attn_bf16(const void *xn, const void *wq, const void *qnw, const void *k, const void *v, void *ao,
-                           int B, int S, int H, int KV, int Lenc, int D, float eps, float scale, int force,
-                           int *path, void *stream) {
-    if (!xn || !wq || !qnw || !k || !v || !ao || !path) return fail(ACEHIP_E_ARG, "cross_attn: null argument");
-    if (B <= 0 || S <= 0 || H <= 0 || KV <= 0 || Lenc <= 0 || D <= 0 || D % 64 || H % 2 || (int64_t)B * S > INT32_MAX)
-        return fail(ACEHIP_E_ARG, "cross_attn: shape");
-    if (force < -1 || force > 1) return fail(ACEHIP_E_ARG, "cross_attn: force must be -1, 0 or 1");
-    *path = -1;
-    hipStream_t s = (hipStream_t)stream;
-    GemmArgs cq = lin_headpost((const bf16_t *)xn, D, (const bf16_t *)wq, D, B, S, H, 0, 0, (const bf16_t *)qnw, nullptr,
-                               nullptr, nullptr, eps, HeadDst{nullptr, nullptr, nullptr, S, 0});
-    cq.ws = abi_gemm_ws();
-    cq.ws_bytes = cq.ws ? GEMM_WS_BYTES : 0;
-    const int64_t qd = (int64_t)H * 128;
-    const bool shape = cross_fuse_shape(cq, KV, Lenc);
-    const bool planned = shape && cross_fuse_planned(cq) && attention_whole_units(B, H, KV, S, Lenc, true);
-    // force = 1: fused wherever the kernel can run the shape; 0: the two launches it fuses
-    // (variant 13 + whole units on attn_fwd_kernel); −1: forward_body's own choice
-    const bool fused = shape && (force == 1 || (force < 0 && planned && knobs().cross_fuse));
-    if (fused) {
-        *path = 1;
-        return cross_q_attention(cq, (const bf16_t *)k, (const bf16_t *)v, (bf16_t *)ao, KV, Lenc, scale, qd, s);
-    }
-    *path = 0;
-    cq.hp.q = abi_cross_q((size_t)B * S * qd * sizeof(bf16_t));
-    if (!cq.hp.q) return fail(ACEHIP_E_OOM, "cross_attn: Q scratch");
-    if (force == 0 || planned) {
-        if (H != 2 * KV) return fail(ACEHIP_E_ARG, "cross_attn: the forced two-launch path needs H = 2 KV");
-        if (int rc = gemm_variant(cq, 13, s)) return rc;
-        return attention_fwd_units(cq.hp.q, (const bf16_t *)k, (const bf16_t *)v, (bf16_t *)ao, B, H, KV, S, Lenc,
-                                   scale, qd, s);
-    }
-    if (int rc = gemm(cq, s)) return rc;
-    return acehip_attention_bf16(cq.hp.q, k, v, ao, B, H, KV, S, Lenc, -1, scale, stream);
-}
-
-int acehip_attention_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV,
-                          int Sq, int Sk, int window, float scale, void *stream) {
-    return acehip_attention_masked_bf16(q, k, v, o, B, H, KV, Sq, Sk, window, scale, nullptr, stream);
-}
-
-int acehip_attention_probs_bf16(const void *q, const void *k, int B, int H, int KV, int Sq, int Sk, const int *heads,
-                                int n, int k0, int k1, float scale, float *out, void *stream) {
-    if (!q || !k || !heads || !out) return fail(ACEHIP_E_ARG, "attention_probs: null argument");
-    if (n < 1 || n > 64) return fail(ACEHIP_E_ARG, "attention_probs: n must be in [1, 64]");
-    AttnProbsSel sel;
-    sel.n = n;
-    for (int i = 0; i < n; ++i) {
-        if (heads[i] < 0 || heads[i] >= H) return fail(ACEHIP_E_ARG, "attention_probs: head index out of range");
-        sel.head[i] = (int16_t)heads[i];
-        sel.slot[i] = (int16_t)i;
-    }
-    return attention_probs((const bf16_t *)q, (const bf16_t *)k, B, H, KV, Sq, Sk, sel, k0, k1, scale, out,
-                           (hipStream_t)stream);
-}
-
-int acehip_attention_masked_bf16(const void *q, const void *k, const void *v, void *o, int B, int H, int KV,
-                                 int Sq, int Sk, int window, float scale, const uint8_t *kmask, void *stream) {
-    // standalone entry (tests / micro-bench): one lazily allocated tail-split workspace
-    // per device (the DiT runtime owns its own, allocated at create)
-    static std::map<int, void *> ws_by_dev;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    void *&ws = ws_by_dev[dev];
-    if (!ws) {
-        const size_t wb = attention_ws_bytes();
-        if (hipMalloc(&ws, wb) != hipSuccess) return fail(ACEHIP_E_OOM, "attention workspace");
-        HIP_TRY(hipMemset(ws, 0, wb));
-    }
-    return attention((const bf16_t *)q, (const bf16_t *)k, (const bf16_t *)v, (bf16_t *)o, B, H, KV, Sq,
-                     Sk, window, scale, (int64_t)H * 128, ws, (hipStream_t)stream, kmask);
-}
-
 }  // extern "C"
-
-// ===================================================================== fp32 ====
-// The fp32 parity mode (acehip_dit_cfg.fp32 = 1): the reference's
-// fp32 forward (what it runs on a non-cuda device, init_service_orchestrator.py:51)
-// with fp32 weights and activations throughout, on the kernels of f32.hip.  No
-// algebraic shortcuts (no CFG-row dedup, no closed-form null rows, no graphs).
-
-static float *falloc(acehip_dit *h, size_t elems) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(elems, 1) * 4) != hipSuccess) return nullptr;
-    h->allocs.push_back(p);
-    return (float *)p;
-}
-
-static void add_slot_f32(acehip_dit *h, const std::string &name, float *dst, std::vector<int64_t> shape,
-                         PackKind kind = P_F32) {
-    Slot s;
-    s.dst_f32 = dst;
-    s.shape = std::move(shape);
-    s.kind = kind;
-    h->slots[name] = s;
-}
-
-static int create_f32(acehip_dit *h) {
-    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, L = h->L;
-    bool ok = true;
-    auto A = [&](size_t n) { float *p = falloc(h, n); ok = ok && p; return p; };
-    auto &f = h->f;
-    f.tables = A((size_t)L * 6 * D);
-    f.layers.resize(L);
-    for (int i = 0; i < L && ok; ++i) {
-        auto &ly = f.layers[i];
-        ly.n_sa = A(D); ly.n_ca = A(D); ly.n_mlp = A(D);
-        ly.wqkv = A((size_t)(qd + 2 * kvd) * D); ly.wo = A((size_t)D * qd);
-        ly.qn = A(128); ly.kn = A(128); ly.cqn = A(128); ly.ckn = A(128);
-        ly.wcq = A((size_t)qd * D); ly.wckv = A((size_t)2 * kvd * D); ly.wco = A((size_t)D * qd);
-        ly.wg = A((size_t)F * D); ly.wu = A((size_t)F * D); ly.wdown = A((size_t)D * F);
-        if (!ok) break;
-        const std::string p = "layers." + std::to_string(i);
-        add_slot_f32(h, p + ".scale_shift_table", f.tables + (size_t)i * 6 * D, {1, 6, D});
-        add_slot_f32(h, p + ".self_attn_norm.weight", ly.n_sa, {D});
-        add_slot_f32(h, p + ".cross_attn_norm.weight", ly.n_ca, {D});
-        add_slot_f32(h, p + ".mlp_norm.weight", ly.n_mlp, {D});
-        add_slot_f32(h, p + ".self_attn.q_proj.weight", ly.wqkv, {qd, D});
-        add_slot_f32(h, p + ".self_attn.k_proj.weight", ly.wqkv + (size_t)qd * D, {kvd, D});
-        add_slot_f32(h, p + ".self_attn.v_proj.weight", ly.wqkv + (size_t)(qd + kvd) * D, {kvd, D});
-        add_slot_f32(h, p + ".self_attn.o_proj.weight", ly.wo, {D, qd});
-        add_slot_f32(h, p + ".self_attn.q_norm.weight", ly.qn, {128});
-        add_slot_f32(h, p + ".self_attn.k_norm.weight", ly.kn, {128});
-        add_slot_f32(h, p + ".cross_attn.q_proj.weight", ly.wcq, {qd, D});
-        add_slot_f32(h, p + ".cross_attn.k_proj.weight", ly.wckv, {kvd, D});
-        add_slot_f32(h, p + ".cross_attn.v_proj.weight", ly.wckv + (size_t)kvd * D, {kvd, D});
-        add_slot_f32(h, p + ".cross_attn.o_proj.weight", ly.wco, {D, qd});
-        add_slot_f32(h, p + ".cross_attn.q_norm.weight", ly.cqn, {128});
-        add_slot_f32(h, p + ".cross_attn.k_norm.weight", ly.ckn, {128});
-        add_slot_f32(h, p + ".mlp.gate_proj.weight", ly.wg, {F, D});
-        add_slot_f32(h, p + ".mlp.up_proj.weight", ly.wu, {F, D});
-        add_slot_f32(h, p + ".mlp.down_proj.weight", ly.wdown, {D, F});
-    }
-    f.sst_out = A(2 * D); f.win = A((size_t)D * 384); f.bin = A(D);
-    f.wce = A((size_t)D * D); f.bce = A(D); f.norm_out = A(D);
-    f.wout = A((size_t)128 * D); f.bout = A(128);
-    const char *te_names[2] = {"time_embed", "time_embed_r"};
-    for (int e = 0; e < 2 && ok; ++e) {
-        f.te_l1[e] = A((size_t)D * 256); f.te_b1[e] = A(D);
-        f.te_l2[e] = A((size_t)D * D); f.te_b2[e] = A(D);
-        f.te_tp[e] = A((size_t)6 * D * D); f.te_btp[e] = A(6 * D);
-        if (!ok) break;
-        const std::string p = te_names[e];
-        add_slot_f32(h, p + ".linear_1.weight", f.te_l1[e], {D, 256});
-        add_slot_f32(h, p + ".linear_1.bias", f.te_b1[e], {D});
-        add_slot_f32(h, p + ".linear_2.weight", f.te_l2[e], {D, D});
-        add_slot_f32(h, p + ".linear_2.bias", f.te_b2[e], {D});
-        add_slot_f32(h, p + ".time_proj.weight", f.te_tp[e], {6 * D, D});
-        add_slot_f32(h, p + ".time_proj.bias", f.te_btp[e], {6 * D});
-    }
-    if (ok) {
-        add_slot_f32(h, "scale_shift_table", f.sst_out, {1, 2, D});
-        add_slot_f32(h, "proj_in.1.weight", f.win, {D, 192, 2}, P_F32_PROJ_IN);
-        add_slot_f32(h, "proj_in.1.bias", f.bin, {D});
-        add_slot_f32(h, "condition_embedder.weight", f.wce, {D, D});
-        add_slot_f32(h, "condition_embedder.bias", f.bce, {D});
-        add_slot_f32(h, "norm_out.weight", f.norm_out, {D});
-        add_slot_f32(h, "proj_out.1.weight", f.wout, {D, 64, 2}, P_F32_PROJ_OUT_W);
-        add_slot_f32(h, "proj_out.1.bias", f.bout, {64}, P_F32_PROJ_OUT_B);
-    }
-    const size_t S = h->cfg.max_S, Bc = h->cfg.max_Bc, M = S * Bc, Le = h->cfg.max_Lenc;
-    f.X = A(M * D); f.XN = A(M * D); f.QKV = A(M * (qd + 2 * kvd));
-    f.Qh = A(M * qd); f.Kh = A(M * kvd); f.Vh = A(M * kvd); f.AO = A(M * qd);
-    f.G = A(M * F); f.U = A(M * F); f.Hb = A(M * F); f.Xin = A(M * 384); f.O2 = A(M * 128);
-    for (int e = 0; e < 2; ++e) { f.emb[e] = A(Bc * 256); f.temb_e[e] = A(Bc * D); f.proj_e[e] = A(Bc * 6 * D); }
-    f.h1 = A(Bc * D); f.temb = A(Bc * D); f.proj = A(Bc * 6 * D);
-    f.mod = A((size_t)L * Bc * 6 * D); f.mod_out = A(Bc * 2 * D);
-    f.Kc = A((size_t)L * Bc * kvd * Le); f.Vc = A((size_t)L * Bc * kvd * Le);
-    f.E = A(Bc * Le * D); f.KVtmp = A(Bc * Le * 2 * kvd);
-    f.rope_cos = A(S * 128); f.rope_sin = A(S * 128);
-    h->freqs = A(128);
-    if (!ok) return fail(ACEHIP_E_OOM, "dit_create (fp32): device allocation failed");
-    float fr[128];
-    for (int i = 0; i < 128; ++i) fr[i] = expf((-9.210340371976184f * (float)i) / 128.0f);
-    HIP_TRY(hipMemcpy(h->freqs, fr, sizeof(fr), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// every fp32 weight goes through the host (parity mode: load time is not a concern)
-static int set_weight_f32(acehip_dit *h, Slot &s, const void *ptr, int dtype, int64_t n, int on_device) {
-    std::vector<float> v(n);
-    if (dtype == ACEHIP_F32) {
-        HIP_TRY(hipMemcpy(v.data(), ptr, n * 4, on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-    } else {
-        std::vector<bf16_t> b(n);
-        HIP_TRY(hipMemcpy(b.data(), ptr, n * 2, on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        for (int64_t i = 0; i < n; ++i) v[i] = bf2f(b[i]);
-    }
-    std::vector<float> out;
-    const std::vector<float> *src = &v;
-    if (s.kind == P_F32_PROJ_IN) {            // [D][192][2] → [D][k·192 + c]
-        const int64_t D = s.shape[0];
-        out.resize(n);
-        for (int64_t o = 0; o < D; ++o)
-            for (int c = 0; c < 192; ++c)
-                for (int k = 0; k < 2; ++k) out[o * 384 + k * 192 + c] = v[(o * 192 + c) * 2 + k];
-        src = &out;
-    } else if (s.kind == P_F32_PROJ_OUT_W) {  // [D][64][2] → [k·64 + o][D]
-        const int64_t D = s.shape[0];
-        out.resize(n);
-        for (int64_t c = 0; c < D; ++c)
-            for (int o = 0; o < 64; ++o)
-                for (int k = 0; k < 2; ++k) out[(k * 64 + o) * D + c] = v[(c * 64 + o) * 2 + k];
-        src = &out;
-    } else if (s.kind == P_F32_PROJ_OUT_B) {  // [64] → [k·64 + o]
-        out.resize(128);
-        for (int k = 0; k < 2; ++k)
-            for (int o = 0; o < 64; ++o) out[k * 64 + o] = v[o];
-        src = &out;
-    } else if (s.kind != P_F32) {
-        return fail(ACEHIP_E_ARG, "dit_set_weight (fp32): unexpected slot");
-    }
-    HIP_TRY(hipMemcpy(s.dst_f32, src->data(), src->size() * 4, hipMemcpyHostToDevice));
-    s.set = true;
-    return 0;
-}
-
-// Qwen3RotaryEmbedding in fp32: inv_freq stays fp32 (no .to(bf16) in an fp32 model),
-// angle = fp32(pos · inv_freq), cos/sin of it
-static int build_rope_f32(acehip_dit *h) {
-    const int hd = h->cfg.head_dim, S = h->cfg.max_S;
-    std::vector<float> inv(hd / 2);
-    for (int i = 0; i < hd / 2; ++i)
-        inv[i] = !h->inv_freq_override.empty() ? h->inv_freq_override[i]
-                                               : 1.0f / powf(h->cfg.rope_theta, (float)(2 * i) / (float)hd);
-    std::vector<float> c((size_t)S * hd), sn((size_t)S * hd);
-    for (int p = 0; p < S; ++p)
-        for (int i = 0; i < hd; ++i) {
-            const float a = (float)p * inv[i % (hd / 2)];
-            c[(size_t)p * hd + i] = (float)cos((double)a);
-            sn[(size_t)p * hd + i] = (float)sin((double)a);
-        }
-    HIP_TRY(hipMemcpy(h->f.rope_cos, c.data(), c.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->f.rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-    return 0;
-}
-
-static int set_condition_f32(acehip_dit *h, const float *enc, int Bc, int Lenc, hipStream_t s) {
-    auto &f = h->f;
-    const int D = h->D, kvd = h->kvd, M = Bc * Lenc;
-    int rc;
-    GemmF32Args g{};
-    g.A = enc; g.lda = D; g.W = f.wce; g.ldw = D; g.C = f.E; g.ldc = D; g.M = M; g.N = D; g.K = D;
-    g.epi = EPI_STORE; g.bias = f.bce;
-    if ((rc = gemm_f32(g, s))) return rc;
-    const size_t per = (size_t)Bc * kvd * Lenc;
-    for (int l = 0; l < h->L; ++l) {
-        GemmF32Args k{};
-        k.A = f.E; k.lda = D; k.W = f.layers[l].wckv; k.ldw = D; k.C = f.KVtmp; k.ldc = 2 * kvd;
-        k.M = M; k.N = 2 * kvd; k.K = D; k.epi = EPI_STORE;
-        if ((rc = gemm_f32(k, s))) return rc;
-        HeadPostF32Args p{};
-        p.src = f.KVtmp; p.ld_src = 2 * kvd; p.B = Bc; p.S = Lenc; p.nq = 0;
-        p.nk = h->cfg.kv_heads; p.nv = h->cfg.kv_heads; p.kw = f.layers[l].ckn;
-        p.k = f.Kc + l * per; p.v = f.Vc + l * per; p.S_dst = Lenc; p.eps = h->cfg.eps;
-        if ((rc = head_post_f32(p, s))) return rc;
-    }
-    h->have_cond = true;
-    h->cond_Bc = Bc;
-    h->cond_Lenc = Lenc;
-    h->uniform_from = 1 << 30;
-    return 0;
-}
-
-static int forward_f32(acehip_dit *h, const float *xt, const float *ctx, int Bx, const float *t, const float *t_r,
-                       int t_stride, int Bc, int T, float *vt_out, hipStream_t s, const acehip_attn_capture *cap) {
-    auto &f = h->f;
-    const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd, L = h->L, S = (T + 1) / 2, M = Bc * S;
-    const int H = h->cfg.heads, KV = h->cfg.kv_heads, Le = h->cond_Lenc;
-    const float eps = h->cfg.eps, scale = 1.0f / sqrtf((float)h->cfg.head_dim);
-    const int64_t mbs = 6 * D;
-    const size_t cper = (size_t)Bc * kvd * Le;
-    int rc;
-#define RUN(x) do { if ((rc = (x))) return rc; } while (0)
-    auto gemm = [&](const float *A, int lda, const float *W, float *C, int ldc, int m, int n, int k, const float *bias,
-                    int epi, const float *gate = nullptr) {
-        GemmF32Args g{};
-        g.A = A; g.lda = lda; g.W = W; g.ldw = k; g.C = C; g.ldc = ldc; g.M = m; g.N = n; g.K = k; g.bias = bias;
-        g.epi = epi; g.res = C; g.ldr = ldc; g.gate = gate; g.gate_bstride = mbs; g.rows_per_batch = S;
-        return gemm_f32(g, s);
-    };
-    // timestep embeddings (base:225-254, :1340-1344)
-    for (int e = 0; e < 2; ++e) {
-        RUN(timestep_sinusoid_f32(t, t_r, t_stride, e, Bc, h->freqs, f.emb[e], s));
-        RUN(gemv_f32(f.emb[e], 256, f.te_l1[e], f.te_b1[e], f.h1, D, Bc, D, 256, 0, s));
-        RUN(gemv_f32(f.h1, D, f.te_l2[e], f.te_b2[e], f.temb_e[e], D, Bc, D, D, 1, s));
-        RUN(gemv_f32(f.temb_e[e], D, f.te_tp[e], f.te_btp[e], f.proj_e[e], 6 * D, Bc, 6 * D, D, 1, s));
-    }
-    RUN(add_f32(f.temb_e[0], f.temb_e[1], f.temb, (int64_t)Bc * D, s));
-    RUN(add_f32(f.proj_e[0], f.proj_e[1], f.proj, (int64_t)Bc * 6 * D, s));
-    RUN(modulation_f32(f.tables, L, 6, f.proj, Bc, D, f.mod, s));
-    RUN(modulation_f32(f.sst_out, 1, 2, f.temb, Bc, D, f.mod_out, s));
-    // concat + pad + proj_in (base:1347-1358)
-    RUN(pack_patches_f32(xt, ctx, Bx, Bc, T, S, f.Xin, s));
-    RUN(gemm(f.Xin, 384, f.win, f.X, D, M, D, 384, f.bin, EPI_STORE));
-    for (int l = 0; l < L; ++l) {
-        const auto &ly = f.layers[l];
-        const float *md = f.mod + (size_t)l * Bc * 6 * D;
-        // self-attention, AdaLN-Zero (base:499-511)
-        RUN(rmsnorm_f32(f.X, ly.n_sa, md + 0 * D, md + 1 * D, mbs, S, f.XN, M, D, eps, s));
-        RUN(gemm(f.XN, D, ly.wqkv, f.QKV, qd + 2 * kvd, M, qd + 2 * kvd, D, nullptr, EPI_STORE));
-        HeadPostF32Args p{};
-        p.src = f.QKV; p.ld_src = qd + 2 * kvd; p.B = Bc; p.S = S; p.nq = H; p.nk = KV; p.nv = KV;
-        p.qw = ly.qn; p.kw = ly.kn; p.cos = f.rope_cos; p.sin = f.rope_sin;
-        p.q = f.Qh; p.k = f.Kh; p.v = f.Vh; p.S_dst = S; p.eps = eps;
-        RUN(head_post_f32(p, s));
-        AttnF32Args at{};
-        at.q = f.Qh; at.k = f.Kh; at.v = f.Vh; at.o = f.AO; at.o_ld = qd; at.B = Bc; at.H = H; at.KV = KV;
-        at.Sq = S; at.Sk = S; at.window = h->sliding[l] ? h->cfg.window : -1; at.scale = scale;
-        RUN(attention_f32(at, s));
-        RUN(gemm(f.AO, qd, ly.wo, f.X, D, M, D, qd, nullptr, EPI_GATED_RES, md + 2 * D));
-        // cross-attention, plain residual (base:513-526)
-        RUN(rmsnorm_f32(f.X, ly.n_ca, nullptr, nullptr, 0, S, f.XN, M, D, eps, s));
-        RUN(gemm(f.XN, D, ly.wcq, f.QKV, qd, M, qd, D, nullptr, EPI_STORE));
-        HeadPostF32Args cq{};
-        cq.src = f.QKV; cq.ld_src = qd; cq.B = Bc; cq.S = S; cq.nq = H; cq.qw = ly.cqn; cq.q = f.Qh;
-        cq.S_dst = S; cq.eps = eps;
-        RUN(head_post_f32(cq, s));
-        AttnProbsSel sel;
-        if (cap && capture_layer(cap, l, sel)) {   // acehip_dit_forward_capture (see forward_body)
-            RUN(attention_probs_f32(f.Qh, f.Kc + l * cper, Bc, H, KV, S, Le, sel, cap->k0, cap->k1, scale, cap->out, s));
-            if (cap->stop_after_last && l == capture_last_layer(cap)) return 0;
-        }
-        AttnF32Args ca{};
-        ca.q = f.Qh; ca.k = f.Kc + l * cper; ca.v = f.Vc + l * cper; ca.o = f.AO; ca.o_ld = qd; ca.B = Bc;
-        ca.H = H; ca.KV = KV; ca.Sq = S; ca.Sk = Le; ca.window = -1; ca.scale = scale;
-        RUN(attention_f32(ca, s));
-        RUN(gemm(f.AO, qd, ly.wco, f.X, D, M, D, qd, nullptr, EPI_RES));
-        // SwiGLU MLP, AdaLN-Zero (base:528-533)
-        RUN(rmsnorm_f32(f.X, ly.n_mlp, md + 3 * D, md + 4 * D, mbs, S, f.XN, M, D, eps, s));
-        RUN(gemm(f.XN, D, ly.wg, f.G, F, M, F, D, nullptr, EPI_STORE));
-        RUN(gemm(f.XN, D, ly.wu, f.U, F, M, F, D, nullptr, EPI_STORE));
-        RUN(swiglu_f32(f.G, f.U, f.Hb, (int64_t)M * F, s));
-        RUN(gemm(f.Hb, F, ly.wdown, f.X, D, M, D, F, nullptr, EPI_GATED_RES, md + 5 * D));
-    }
-    // norm_out AdaLN + proj_out + crop (base:1491-1501)
-    RUN(rmsnorm_f32(f.X, f.norm_out, f.mod_out, f.mod_out + D, 2 * D, S, f.XN, M, D, eps, s));
-    RUN(gemm(f.XN, D, f.wout, T % 2 == 0 ? vt_out : f.O2, 128, M, 128, D, f.bout, EPI_STORE));
-    if (T % 2) RUN(crop_rows_f32(f.O2, Bc, 2 * S, T, 64, vt_out, s));
-#undef RUN
-    return 0;
-}

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "layer_args.h"
+#include "weights.h"
 #include "../../include/acehip.h"
 
 using namespace acehip;
@@ -53,14 +54,7 @@ struct acehip_enc {
     int D = 0, F = 0, qd = 0, kvd = 0, L = 0;
     bool finalized = false;
     std::vector<void *> allocs;
-    enum Pack { P_COPY, P_GU_GATE, P_GU_UP };   // gate / up: interleaved panels (pack_gate_up)
-    struct Slot {
-        bf16_t *dst;
-        std::vector<int64_t> shape;
-        Pack kind;
-        bool set;
-    };
-    std::map<std::string, Slot> slots;
+    acehip::WeightTable weights;   // state-dict names → the buffers below (gate / up interleaved into wgu)
     struct Layer { bf16_t *ln1, *ln2, *wqkv, *wo, *qn, *kn, *wgu, *wdown; };
     std::vector<Layer> layers;
     bf16_t *wemb = nullptr, *bemb = nullptr, *norm = nullptr, *wout = nullptr, *bout = nullptr;
@@ -123,9 +117,8 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
     const int D = h->D, F = h->F, qd = h->qd, kvd = h->kvd;
     bool ok = true;
     auto A = [&](size_t n) { bf16_t *p = dev_alloc(h->allocs, n); ok = ok && p; return p; };
-    auto slot = [&](const std::string &n, bf16_t *dst, std::vector<int64_t> shape,
-                    acehip_enc::Pack kind = acehip_enc::P_COPY) {
-        h->slots[n] = acehip_enc::Slot{dst, std::move(shape), kind, false};
+    auto slot = [&](const std::string &n, bf16_t *dst, std::vector<int64_t> shape, Pack kind = Pack::COPY) {
+        h->weights.add(n, dst, std::move(shape), kind);
     };
     h->layers.resize(h->L);
     for (int i = 0; i < h->L && ok; ++i) {
@@ -143,8 +136,8 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
         slot(p + ".self_attn.o_proj.weight", ly.wo, {D, qd});
         slot(p + ".self_attn.q_norm.weight", ly.qn, {128});
         slot(p + ".self_attn.k_norm.weight", ly.kn, {128});
-        slot(p + ".mlp.gate_proj.weight", ly.wgu, {F, D}, acehip_enc::P_GU_GATE);
-        slot(p + ".mlp.up_proj.weight", ly.wgu, {F, D}, acehip_enc::P_GU_UP);
+        slot(p + ".mlp.gate_proj.weight", ly.wgu, {F, D}, Pack::GU_GATE);
+        slot(p + ".mlp.up_proj.weight", ly.wgu, {F, D}, Pack::GU_UP);
         slot(p + ".mlp.down_proj.weight", ly.wdown, {D, F});
     }
     if (ok && cfg->in_dim) {
@@ -195,52 +188,23 @@ int acehip_enc_create(int device, const acehip_enc_cfg *cfg, acehip_enc **out) {
 int acehip_enc_set_weight(acehip_enc *h, const char *name, const void *ptr, int dtype, int ndim,
                           const int64_t *shape, int on_device) {
     if (!h || !name || !ptr || !shape || ndim <= 0) return fail(ACEHIP_E_ARG, "enc_set_weight: null argument");
-    if (dtype != ACEHIP_F32 && dtype != ACEHIP_BF16) return fail(ACEHIP_E_ARG, "enc_set_weight: dtype");
     HIP_TRY(hipSetDevice(h->device));
     const std::string nm(name);
     if (nm == "_rope_inv_freq") {   // the caller's torch fp32 inv_freq (exact reference constant)
         if (dtype != ACEHIP_F32 || shape[0] != 64) return fail(ACEHIP_E_ARG, "_rope_inv_freq: fp32 [64]");
-        h->inv_freq_override.resize(64);
-        HIP_TRY(hipMemcpy(h->inv_freq_override.data(), ptr, 256,
-                          on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
-        return 0;
+        return fetch_host_f32(ptr, dtype, 64, on_device, h->inv_freq_override);
     }
     if (nm == "rotary_emb.inv_freq") return 0;   // non-persistent buffer, recomputed
-    auto it = h->slots.find(nm);
-    if (it == h->slots.end()) return fail(ACEHIP_E_NAME, "enc_set_weight: unknown weight " + nm);
-    auto &s = it->second;
-    if (std::vector<int64_t>(shape, shape + ndim) != s.shape)
-        return fail(ACEHIP_E_ARG, "enc_set_weight: shape mismatch for " + nm);
-    int64_t n = 1;
-    for (auto v : s.shape) n *= v;
-    // stage through the host as bf16 (load time only; RNE like torch's .to(bfloat16))
-    std::vector<bf16_t> hb(n);
-    const hipMemcpyKind k = on_device ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
-    if (dtype == ACEHIP_F32) {
-        std::vector<float> f(n);
-        HIP_TRY(hipMemcpy(f.data(), ptr, n * 4, k));
-        for (int64_t i = 0; i < n; ++i) hb[i] = f2bf(f[i]);
-    } else {
-        HIP_TRY(hipMemcpy(hb.data(), ptr, n * 2, k));
-    }
-    if (s.kind != acehip_enc::P_COPY) {
-        const int rc = pack_gate_up(s.dst, hb.data(), s.shape[0], s.shape[1], s.kind == acehip_enc::P_GU_UP,
-                                    hipMemcpyHostToDevice);
-        if (rc) return rc;
-    } else {
-        HIP_TRY(hipMemcpy(s.dst, hb.data(), n * 2, hipMemcpyHostToDevice));
-    }
-    s.set = true;
-    return 0;
+    WeightSlot *s = nullptr;
+    if (int rc = h->weights.find_checked(nm, ndim, shape, "enc_set_weight", s)) return rc;
+    // the handle keeps no staging buffer: fp32 is cast through a temporary
+    return load_weight(*s, "enc_set_weight", nm, ptr, dtype, on_device, Staging{});
 }
 
 int acehip_enc_finalize(acehip_enc *h) {
     if (!h) return fail(ACEHIP_E_ARG, "null handle");
     HIP_TRY(hipSetDevice(h->device));
-    std::string missing;
-    for (auto &kv : h->slots)
-        if (!kv.second.set) missing += kv.first + " ";
-    if (!missing.empty()) return fail(ACEHIP_E_STATE, "enc_finalize: missing weights: " + missing.substr(0, 400));
+    if (int rc = h->weights.missing("enc_finalize")) return rc;
     if (h->F % 32) return fail(ACEHIP_E_ARG, "intermediate must be a multiple of 32");
     const int rc = build_rope_tables(h->cfg.head_dim, h->cfg.max_S, h->cfg.rope_theta, h->inv_freq_override,
                                      h->rope_cos, h->rope_sin);

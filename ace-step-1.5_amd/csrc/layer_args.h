@@ -1,6 +1,6 @@
-// layer_args.h — host pieces the DiT and encoder runtimes (dit.hip, encoder.hip) share: the
-// GemmArgs of a transformer layer's Linear shapes, the GEMM call through a handle's split-K
-// workspace, the RoPE tables, handle-owned device memory and the gate/up weight packing.
+// layer_args.h — host pieces the DiT and encoder runtimes (dit.hip, encoder.hip) and the
+// stand-alone entries (abi.hip) share: the GemmArgs of a transformer layer's Linear shapes, the
+// GEMM call through a handle's split-K workspace and the RoPE tables.  Weight loading: weights.h.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -67,14 +67,6 @@ inline int hgemm(Handle *h, GemmArgs g, hipStream_t s, RowAdd *defer = nullptr) 
     return gemm(g, s, defer);
 }
 
-// `elems` bf16 elements of device memory, freed with the handle (its `allocs`); null on failure
-inline bf16_t *dev_alloc(std::vector<void *> &allocs, size_t elems) {
-    void *p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(elems, 1) * 2) != hipSuccess) return nullptr;
-    allocs.push_back(p);
-    return (bf16_t *)p;
-}
-
 // Qwen3RotaryEmbedding tables cos / sin [max_S][head_dim] in bf16; inv_freq from theta, or the
 // caller's fp32 override ([head_dim / 2], the exact reference constant)
 inline int build_rope_tables(int head_dim, int max_S, float theta, const std::vector<float> &inv_freq_override,
@@ -96,12 +88,4 @@ inline int build_rope_tables(int head_dim, int max_S, float theta, const std::ve
     HIP_TRY(hipMemcpy(sin_dst, s.data(), s.size() * 2, hipMemcpyHostToDevice));
     return 0;
 }
-
-// gate_proj / up_proj [F][K] (contiguous bf16 at src) into the SwiGLU epilogue's layout at dst
-// [2F][K]: 64-row panels of 32 gate rows, then the 32 up rows of the same outputs
-inline int pack_gate_up(bf16_t *dst, const bf16_t *src, int64_t F, int64_t K, bool is_up, hipMemcpyKind kind) {
-    HIP_TRY(hipMemcpy2D(dst + (is_up ? 32 * K : 0), 64 * K * 2, src, 32 * K * 2, 32 * K * 2, F / 32, kind));
-    return 0;
-}
-
 }  // namespace acehip

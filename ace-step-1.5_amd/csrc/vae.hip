@@ -17,6 +17,7 @@
 
 #include "kernels.h"
 #include "conv.h"
+#include "weights.h"
 #include "../../include/acehip.h"
 
 using namespace acehip;
@@ -62,6 +63,7 @@ struct acehip_vae {
     int hop = 1;
     std::vector<void *> allocs;
     std::map<std::string, Raw> raw;
+    Staging stage;              // fp32 -> bf16 cast buffer of the weight load: first fp32 weight .. finalize
     bool finalized = false;
     // decoder
     ConvL dconv1;
@@ -86,6 +88,14 @@ void *valloc(acehip_vae *h, size_t bytes) {
     if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
     h->allocs.push_back(p);
     return p;
+}
+
+// fp32 weights are cast in chunks of this size; the largest Oobleck tensor (2048 x 1024 x 7 fp32,
+// 56 MiB) still goes in one
+constexpr size_t kStageBytes = (size_t)64 << 20;
+void free_stage(acehip_vae *h) {
+    if (h->stage.p) (void)hipFree(h->stage.p);
+    h->stage = Staging{};
 }
 
 std::string norm_name(std::string n) {
@@ -362,19 +372,13 @@ int acehip_vae_set_weight(acehip_vae *h, const char *name, const void *ptr, int 
     r.shape = sh;
     r.p = (bf16_t *)valloc(h, (size_t)n * 2);
     if (!r.p) return fail(ACEHIP_E_OOM, "vae_set_weight: oom");
-    const hipMemcpyKind kd = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (dtype == ACEHIP_BF16) {
-        HIP_TRY(hipMemcpy(r.p, ptr, n * 2, kd));
-    } else if (dtype == ACEHIP_F32) {
-        float *tmp = (float *)valloc(h, (size_t)n * 4);
-        if (!tmp) return fail(ACEHIP_E_OOM, "vae_set_weight: oom");
-        HIP_TRY(hipMemcpy(tmp, ptr, n * 4, kd));
-        int rc = cast_f32_bf16(tmp, r.p, n, 0);
-        if (rc) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-    } else {
-        return fail(ACEHIP_E_ARG, "vae_set_weight: dtype");
+    if (dtype != ACEHIP_BF16 && dtype != ACEHIP_F32) return fail(ACEHIP_E_ARG, "vae_set_weight: unsupported dtype code for " + nm);
+    // fp32 input is cast on the device in chunks through one staging buffer, kept until finalize
+    if (dtype == ACEHIP_F32 && !h->stage.p) {
+        if (hipMalloc(&h->stage.p, kStageBytes) != hipSuccess) return fail(ACEHIP_E_OOM, "vae_set_weight: oom");
+        h->stage.bytes = kStageBytes;
     }
+    if (int rc = fetch_dev_bf16(ptr, dtype, n, on_device, r.p, h->stage)) return rc;
     h->raw[nm] = r;
     return 0;
 }
@@ -440,6 +444,7 @@ int acehip_vae_finalize(acehip_vae *h) {
         if ((rc = make_conv(h, "encoder.conv2", dm, c.encoder_hidden, 3, 1, false, true, h->econv2))) return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
+    free_stage(h);
     h->finalized = true;
     return 0;
 }
@@ -654,6 +659,7 @@ int acehip_vae_destroy(acehip_vae *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     for (void *p : h->allocs) (void)hipFree(p);
+    free_stage(h);
     delete h;
     return 0;
 }
